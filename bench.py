@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json metric on MI355X: Msamples/s of the spectral path tracer on the
 1M-triangle Cornell scene (config C4: 1920x1080, sobol/1024-spp schedule, `direct` integrator), tile-sharded
-over N GPUs with one RCCL reduce of the float framebuffer, plus the traversal kernel's algorithmic
-bandwidth against the HBM roofline and the CPU checker timed on the host cores beside it.
+over N GPUs with one RCCL reduce of the float framebuffer.  With --full the line also carries the traversal kernel's algorithmic
+bandwidth against the HBM roofline, the CPU checker timed on the host cores beside it and the C5 scene's figures.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A step = one iteration = one camera sample (one full path) for every pixel of the frame.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR writes the frame the timed steps leave (what RenderContext.output() hands a
+caller after the reduce) as DIR/<plane>.npy: XYZ sums in float32, sample counts and feedback in float64.
 """
 import argparse
 import json
@@ -21,6 +22,7 @@ sys.path.insert(0, ROOT)
 
 W, H, SPP, NTRI = 1920, 1080, 1024, 1_000_000
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6.3 TB/s is the achievable copy rate
+DUMP_LIMIT_BYTES = 60_000_000   # --dump-outputs writes at most this much (under 64 MB with the .npy headers); a larger frame is dumped as a fixed, seeded sample of its pixels
 ROOFLINE_ITERS = 16    # iterations of the launch the roofline is measured on (and of the instrumented launch that counts its records):
                        # long enough that the fill and the drain of a launch do not colour the lane statistics
 
@@ -260,6 +262,26 @@ def secondary_c5(device, steps=20, warmup=8):
     return out
 
 
+def dump_outputs(out_dir, planes):
+    """Write `planes` (name -> array over the [H, W] pixel grid) as out_dir/<name>.npy: float planes in float32, integer planes in float64
+    (exact).  A frame larger than DUMP_LIMIT_BYTES is written as the same fixed, seeded sample of pixels for every plane, with the flat
+    pixel indices in pixel_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    planes = {k: np.asarray(v) for k, v in planes.items()}
+    planes = {k: v.astype(np.float32 if v.dtype.kind == "f" else np.float64) for k, v in planes.items()}
+    h, w = next(iter(planes.values())).shape[:2]
+    n_pix = h * w
+    per_pixel = sum(v.nbytes // n_pix for v in planes.values())
+    if n_pix * per_pixel > DUMP_LIMIT_BYTES:
+        k = DUMP_LIMIT_BYTES // (per_pixel + 8)
+        idx = np.sort(np.random.default_rng(12345).choice(n_pix, size=k, replace=False))
+        planes = {name: v.reshape((n_pix,) + v.shape[2:])[idx] for name, v in planes.items()}
+        planes["pixel_index"] = idx.astype(np.float64)
+    for name, v in planes.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -271,9 +293,13 @@ def main():
     ap.add_argument("--workload", choices=("c4", "c5"), default="c4",
                     help="c4 (default, the BASELINE headline): 1M-triangle Cornell box; c5: examples/complex.prc (sky + sun, glass, rough conductor, "
                          "principled, spheres) from its committed array fixture, sobol 4096-spp schedule")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C5 object (`secondary`) a default one-GPU C4 run appends to its line")
-    ap.add_argument("--profile-only", action="store_true", help="skip roofline/cpu passes (for rocprofv3 runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline, the CPU baseline, the C5 scene (`secondary`) and the reduce alone; "
+                         "a plain run times the steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the frame the timed steps computed as DIR/<plane>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the C5 object (`secondary`) a one-GPU C4 run appends to its line")
+    ap.add_argument("--profile-only", action="store_true", help="--full: skip roofline/cpu passes (for rocprofv3 runs)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="N>1 rehearsal on a one-GPU box: every rank renders on device 0 and the collectives run over gloo "
                          "(staged through host memory); exercises tile sharding + reduce end to end, the number is NOT a result")
@@ -296,21 +322,24 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     width, height = args.width, args.height
+    # iterations the scene's sample schedule must cover: the warm-up, the timed steps and (--full) the two roofline passes.  A run that
+    # needs more than the workload's schedule gets a schedule of exactly that length (the sobol table is tabulated per schedule).
+    needed = args.warmup + args.steps + (2 * ROOFLINE_ITERS if args.full and not args.profile_only else 0)
     if args.workload == "c5":
         sc = scene.ArrayScene(os.path.join(ROOT, "tests", "golden", "scenes", "complex_c5.npz"))   # the sky table is rebuilt on load (prgpu_sky_table)
         sc.desc.settings.width, sc.desc.settings.height = width, height
+        if needed > sc.desc.settings.aa_samples:
+            sc.desc.settings.aa_samples = needed
         spp = sc.desc.settings.aa_samples
         workload = ("C5: examples/complex.prc (%d triangles + 4 spheres, sky + sun, glass / rough conductor / principled materials), %dx%d, `direct` "
                     "integrator, sobol %d-spp schedule, hero wavelengths (spd CMIS), %d iterations timed" % (sc.desc.n_triangles, width, height, spp, args.steps))
         variant, what = "255u", "the same scene (complex.prc)"
     else:
-        spp = SPP
-        sc = scene.cornell_soup(width, height, spp=SPP, n_triangles=args.triangles)
+        spp = max(SPP, needed)
+        sc = scene.cornell_soup(width, height, spp=spp, n_triangles=args.triangles)
         workload = ("C4: Cornell box + %d-triangle soup (%d triangles), %dx%d, `direct` integrator (NEE+MIS+RR, depth 64), "
-                    "sobol %d-spp schedule, hero wavelengths (spd CMIS), %d iterations timed" % (args.triangles - 32, args.triangles, width, height, SPP, args.steps))
+                    "sobol %d-spp schedule, hero wavelengths (spd CMIS), %d iterations timed" % (args.triangles - 32, args.triangles, width, height, spp, args.steps))
         variant, what = "0u", "the same 1M-triangle scene"
-    if args.steps + args.warmup + 2 * ROOFLINE_ITERS > spp:
-        raise SystemExit("steps + warmup (+ %d roofline iterations) exceed the %d-spp schedule" % (2 * ROOFLINE_ITERS, spp))
     t0 = time.time()
     ctx = backend.RenderContext(sc, device=local)
     t_create = time.time() - t0
@@ -408,7 +437,7 @@ def main():
     rays = distributed.sum_scalar(sum(after[k] - before[k] for k in ("primary_rays", "bounce_rays", "shadow_rays")), device=dev)
     depth = distributed.sum_scalar(after["camera_depth"] - before["camera_depth"], device=dev)
     own_samples = after["pixel_samples"] - before["pixel_samples"]
-    reduce_ms = distributed.max_scalar(reduce_alone_ms(), device=dev)
+    reduce_ms = distributed.max_scalar(reduce_alone_ms(), device=dev) if args.full else None
     rccl_ranks, rccl_rank = comm.query() if comm is not None else (None, None)   # what the communicator itself says (rank 0 = the root)
 
     out = {
@@ -425,12 +454,20 @@ def main():
                    # ncclCommCount / ncclCommUserRank of the communicator the reduce ran on, read on the root: null when no RCCL communicator exists
                    # (one rank, or the host-staged rehearsal)
                    "rccl_ranks": rccl_ranks if (comm is not None and world > 1) else None, "rccl_rank_of_root": rccl_rank if (comm is not None and world > 1) else None,
-                   "reduce_ms": round(reduce_ms, 4),   # the collective alone (max over ranks), repeated on the finished frame after the timed region
+                   "reduce_ms": round(reduce_ms, 4) if reduce_ms is not None else None,   # --full: the collective alone (max over ranks), repeated on the finished frame after the timed region
                    "reduce_ms_in_timed_region": round((dt - max(x * args.steps * 1e-3 for x in render_ms)) * 1e3, 4),   # wall time after the slowest rank's render
                    "mrays_per_s": round(rays / dt / 1e6, 2), "mean_path_depth": round(depth / max(samples, 1), 3),
                    "scene_create_s": round(t_create, 3)},
     }
 
+    if args.dump_outputs and rank == 0:
+        # the frame a caller of the timed path receives: the root-side sums of the reduce (or, at one rank, the rank's own planes) as
+        # RenderContext.output() downloads them; the torch.distributed fallback sums XYZ and sample counts into the bound tensors
+        if comm is None and world > 1:
+            planes = {"xyz": xyz.cpu().numpy(), "samples": smp.cpu().numpy()}
+        else:
+            planes = dict(zip(("xyz", "samples", "feedback"), ctx.output()))
+        dump_outputs(args.dump_outputs, planes)
     if args.check_frame and rank == 0:
         # the reduced frame must equal a one-rank render of the same iterations (single-tap filter: bit for bit)
         ref = backend.RenderContext(sc, device=local)
@@ -441,7 +478,7 @@ def main():
         gxyz, gsmp = (ctx.output()[:2]) if comm is not None else (xyz.cpu().numpy(), smp.cpu().numpy())
         out["frame_check"] = {"xyz_equal": bool(np.array_equal(gxyz, rxyz)), "samples_equal": bool(np.array_equal(gsmp, rsmp))}
         ref.close()
-    if not args.profile_only:
+    if args.full and not args.profile_only:
         out["roofline"] = roofline(ctx, rank, variant=variant, owned_fraction=own_samples / float(args.steps * width * height),
                                    pmc_workload=(width, height) == (W, H) and (args.workload == "c5" or args.triangles == NTRI))
         if rank == 0 and world == 1 and not args.no_cpu_baseline:

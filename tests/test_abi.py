@@ -236,9 +236,20 @@ def test_cie_tables_of_product_and_checker_are_the_same_data():
     assert a == b
 
 
-def test_no_built_binaries_are_tracked():
+def test_no_built_binaries_are_tracked(tmp_path):
+    """No committed file is an ELF binary.  In a git checkout the committed files are `git ls-files`; a tree exported without its .git
+    holds the committed files next to what building and testing left, so there every file .gitignore does not exclude is checked."""
     import subprocess
-    tracked = subprocess.check_output(["git", "-C", ROOT, "ls-files"]).decode().split()
+    top = subprocess.run(["git", "-C", ROOT, "rev-parse", "--show-toplevel"], capture_output=True, text=True)
+    if top.returncode == 0 and os.path.realpath(top.stdout.strip()) == os.path.realpath(ROOT):
+        tracked = subprocess.check_output(["git", "-C", ROOT, "ls-files", "-z"]).decode().split("\0")
+    else:
+        git = ["git", "--git-dir", str(tmp_path / "index.git"), "--work-tree", ROOT]   # an empty repository: every file is "other"
+        subprocess.check_call(["git", "init", "-q", "--bare", str(tmp_path / "index.git")])
+        tracked = subprocess.check_output(git + ["ls-files", "-z", "--others", "--exclude-standard"]).decode().split("\0")
+        assert "bench.py" in tracked and "tests/test_abi.py" in tracked
+    tracked = [f for f in tracked if f]
+    assert "__graft_entry__.py" in tracked
     for f in tracked:
         with open(os.path.join(ROOT, f), "rb") as fh:
             assert fh.read(4) != b"\x7fELF", f

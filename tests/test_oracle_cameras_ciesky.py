@@ -14,7 +14,7 @@ from pearray_amd import scene
 from test_oracle_skysun import WL, floor_under, light_eval, light_sample
 from test_oracle_inflights import mean_y
 
-REF_EXAMPLES = "/root/reference/examples"
+EXAMPLES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "scenes", "examples")   # the loader's output (tools/make_example_fixtures.py)
 
 
 def camera_scene(setup, width=32, height=16, spp=4):
@@ -180,14 +180,13 @@ def test_uniform_cie_sky_over_a_floor_is_close_to_a_constant_environment():
     assert 0.85 * env < y < env
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_EXAMPLES), reason="reference examples not present")
 def test_reference_examples_with_spherical_and_fisheye_cameras_load():
-    p = scene.PrcScene(path=os.path.join(REF_EXAMPLES, "sky.prc"))
+    p = scene.ArrayScene(os.path.join(EXAMPLES, "sky.npz"))
     cam = p.desc.camera
     assert cam.kind == abi.CAMERA_SPHERICAL and abs(cam.theta_start + 1.570796) < 1e-6 and abs(cam.theta_end - np.pi / 2) < 1e-6
     kinds = sorted(p.desc.lights[i].kind for i in range(p.desc.n_lights))
     assert kinds == [abi.LIGHT_SUN, abi.LIGHT_CIE_SKY] and any(p.desc.lights[i].flags & abi.SKYF_CLOUDY for i in range(p.desc.n_lights))
-    q = scene.PrcScene(path=os.path.join(REF_EXAMPLES, "skylens.prc"))
+    q = scene.ArrayScene(os.path.join(EXAMPLES, "skylens.npz"))
     cam = q.desc.camera
     assert cam.kind == abi.CAMERA_FISHEYE and cam.clip_range == 1 and cam.fisheye_map == abi.FISHEYE_CIRCULAR
     assert abs(cam.fov - np.float32(180.0) * (np.float32(np.pi) / np.float32(180.0))) < 1e-6

@@ -2,6 +2,8 @@
 prgpu_scene_desc, error behaviour.  The checker is pearray_amd.scene.SceneBuilder (the Python scene assembly the parity tests
 use) -- the loader must produce the same description, byte for byte, for the same scene."""
 import ctypes as C
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -12,7 +14,10 @@ from pearray_amd import scene
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SCENES = os.path.join(HERE, "golden", "scenes")
-REF_EXAMPLES = "/root/reference/examples"
+# what the loader made of the reference's examples/*.prc (tools/make_reference_goldens.py): return codes and messages, output channels,
+# digests of complex.prc's arrays, the UV light spectrum; the scenes themselves as array fixtures under golden/scenes
+with open(os.path.join(HERE, "golden", "reference_examples.json")) as _f:
+    REF_GOLDEN = json.load(_f)
 
 
 def arr(ptr, n, dtype):
@@ -171,19 +176,18 @@ def test_two_quads_scene_matches_hand_assembly():
     assert arr(d.tri_material, d.n_triangles, np.uint32).tolist() == [0, 0, 1, 1, 2, 2, 3, 3]
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_EXAMPLES, "cornellbox.prc")), reason="reference checkout not present (GPU box)")
 def test_reference_cornellbox_prc_equals_the_committed_fixture_scene():
-    """examples/cornellbox.prc (+ its include) parsed by the C++ loader == the scene assembled from pearray_amd/data/cornell_box.json
-    (numbers extracted from the same file by tools/extract_fixtures.py).  The file asks for 'vcm': config C1 renders it with `direct`."""
-    s = scene.PrcScene(path=os.path.join(REF_EXAMPLES, "cornellbox.prc"), force_direct=True, width=256, height=256, spp=16)
-    want = scene.cornell_box(256, 256, spp=16)
+    """examples/cornellbox.prc (+ its include) parsed by the C++ loader (golden/scenes/examples/cornellbox.npz, tools/make_example_fixtures.py:
+    96 x 64 pixels, 4 spp) == the scene assembled from pearray_amd/data/cornell_box.json (numbers extracted from the same file by
+    tools/extract_fixtures.py).  The file asks for 'vcm': config C1 renders it with `direct`."""
+    s = scene.ArrayScene(os.path.join(SCENES, "examples", "cornellbox.npz"))
+    want = scene.cornell_box(96, 64, spp=4)
     assert_same_desc(s.desc, want.desc, check_settings=False)
     st = s.desc.settings
-    assert (st.width, st.height, st.aa_sampler, st.aa_samples) == (256, 256, abi.SAMPLER_MJITT, 16)
+    assert (st.width, st.height, st.aa_sampler, st.aa_samples) == (96, 64, abi.SAMPLER_MJITT, 4)
     assert struct_bytes(st) == struct_bytes(want.desc.settings)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_EXAMPLES), reason="reference checkout not present (GPU box)")
 def test_entity_visibility_flags_are_accepted_and_reported_as_inert():
     """SceneLoader.cpp:452-497 stores the flags, Scene.cpp:135,166 traces every ray with MASK_ALL: they change nothing."""
     flagged = scene.PrcScene(source=MINIMAL % "(entity :name 's2' :type 'sphere' :radius 0.5 :material 'm' :camera_visible false :shadow_visible false)")
@@ -193,23 +197,16 @@ def test_entity_visibility_flags_are_accepted_and_reported_as_inert():
 
 
 def test_every_reference_example_either_loads_or_names_what_is_missing():
-    lib = abi.load()
+    """prgpu_prc_load_file on every examples/*.prc, any sky light given a flat table (tools/make_reference_goldens.py records the return
+    codes and messages); every example that loads has its array fixture, or (complex.prc) the C5 fixture."""
     loaded, refused = [], []
-    table = np.full((256, 512, 11), 0.1, dtype=np.float32)
-    sky = (abi.PrcSky * 1)(abi.PrcSky(None, table.ctypes.data_as(C.POINTER(C.c_float)), 512, 256))
-    for name in sorted(os.listdir(REF_EXAMPLES)):
-        if not name.endswith(".prc"):
-            continue
-        h = C.c_void_p()
-        opt = abi.PrcOptions(0, 0, 0, 1, 0)
-        opt.n_skies, opt.skies = 1, sky     # any sky light gets this (flat) table: the Hosek-Wilkie evaluation is the host's
-        rc = lib.prgpu_prc_load_file(os.path.join(REF_EXAMPLES, name).encode(), C.byref(opt), C.byref(h))
+    for name, res in sorted(REF_GOLDEN["load"].items()):
+        rc, msg = res["rc"], res["error"]
         if rc == 0:
             loaded.append(name)
-            lib.prgpu_prc_free(h)
+            assert os.path.exists(os.path.join(SCENES, "examples", name[:-4] + ".npz")) or name == "complex.prc", name
         else:
-            assert rc == -4, (name, rc, lib.prgpu_prc_last_error())   # valid DataLisp, unsupported feature -- never a syntax error
-            msg = lib.prgpu_prc_last_error().decode()
+            assert rc == -4, (name, rc, msg)   # valid DataLisp, unsupported feature -- never a syntax error
             assert "not supported" in msg or "not available" in msg, name
             refused.append(name)
     assert "cornellbox.prc" in loaded and "area_lit_spheres.prc" in loaded and "complex.prc" in loaded and "material_array.prc" in loaded and "sky.prc" in loaded and "skylens.prc" in loaded and "box.prc" in loaded and "quadric_showcase.prc" in loaded and len(loaded) >= 18
@@ -248,13 +245,13 @@ f -4/7/1 -1/8/1 -2/9/1
     assert e.value.args[1] == -4
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_EXAMPLES, "evaluation", "scene.prc")), reason="reference checkout not present (GPU box)")
 def test_reference_evaluation_scene_equals_the_committed_fixture_scene():
-    """examples/evaluation/scene.prc (+ its eight OBJ meshes) through the C++ loader == pearray_amd/data/cbox_eval.json through SceneBuilder."""
-    s = scene.PrcScene(path=os.path.join(REF_EXAMPLES, "evaluation", "scene.prc"))
+    """examples/evaluation/scene.prc (+ its eight OBJ meshes) through the C++ loader (golden/scenes/evaluation.npz,
+    tools/make_reference_goldens.py) == pearray_amd/data/cbox_eval.json through SceneBuilder."""
+    s = scene.ArrayScene(os.path.join(SCENES, "evaluation.npz"))
     want = scene.cbox_eval()
     assert_same_desc(s.desc, want.desc)
-    assert s.outputs()[1] >= 1
+    assert REF_GOLDEN["evaluation_outputs"] >= 1
 
 
 def test_plane_entity_matches_scene_builder():
@@ -357,11 +354,11 @@ def test_sun_position_defaults_to_the_reference_example_value():
     assert abs(np.rad2deg(el.value) - 52.87) < 0.05 and abs(np.rad2deg(az.value) - 143.27) < 0.05   # the comment rounds
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_EXAMPLES), reason="reference checkout absent")
 def test_complex_prc_loads_with_a_host_supplied_sky_table():
-    """BASELINE config C5: examples/complex.prc needs the SkyModel table of its 'sky' light (512 x 256 cells x 11 bands)."""
+    """BASELINE config C5: examples/complex.prc (golden/scenes/complex_c5.npz, tools/make_c5_fixture.py) needs the SkyModel table of its
+    'sky' light (512 x 256 cells x 11 bands)."""
     table = np.full((256, 512, 11), 0.5, dtype=np.float32)
-    s = scene.PrcScene(path=os.path.join(REF_EXAMPLES, "complex.prc"), skies={"sky": table})
+    s = scene.ArrayScene(os.path.join(SCENES, "complex_c5.npz"), sky_tables=[table])
     d = s.desc
     assert (d.settings.width, d.settings.height, d.settings.aa_samples, d.settings.filter_radius) == (1920, 1080, 4096, 0)
     kinds = sorted(d.lights[i].kind for i in range(d.n_lights))
@@ -374,9 +371,11 @@ def test_complex_prc_loads_with_a_host_supplied_sky_table():
     mats = sorted(d.materials[i].kind for i in range(d.n_materials))
     assert abi.MAT_PRINCIPLED in mats and abi.MAT_DIELECTRIC in mats and abi.MAT_LAMBERT in mats
     assert sum(d.entities[i].kind == abi.ENTITY_SPHERE for i in range(d.n_entities)) == 4 and d.n_triangles > 50000
-    ch, n = s.outputs()   # complex.prc:27-34: color (srgb), n, ng, feedback; the commented-out LPE channel is not there
-    assert [(ch[i].kind, ch[i].name) for i in range(n)] == [(abi.CHANNEL_SPECTRAL, b""), (abi.CHANNEL_3D, b"normal"), (abi.CHANNEL_3D, b"normal_geometric"),
-                                                           (abi.CHANNEL_COUNTER, b"feedback")]
+    sky = [d.lights[i] for i in range(d.n_lights) if d.lights[i].kind == abi.LIGHT_SKY][0]
+    assert np.array_equal(arr(d.spectral_tables, d.n_spectral_table_values, np.float32)[sky.table_offset:sky.table_offset + table.size], table.ravel())
+    ch = REF_GOLDEN["complex_outputs"]   # complex.prc:27-34: color (srgb), n, ng, feedback; the commented-out LPE channel is not there
+    assert [(k, name.encode()) for k, name in ch] == [(abi.CHANNEL_SPECTRAL, b""), (abi.CHANNEL_3D, b"normal"), (abi.CHANNEL_3D, b"normal_geometric"),
+                                                      (abi.CHANNEL_COUNTER, b"feedback")]
 
 
 def test_scene_cache_round_trips_a_description_and_drops_sky_tables(tmp_path):
@@ -408,24 +407,22 @@ def test_scene_cache_round_trips_a_description_and_drops_sky_tables(tmp_path):
 
 
 def test_c5_fixture_is_the_reference_scene():
-    """tests/golden/scenes/complex_c5.npz (tools/make_c5_fixture.py) against a fresh load of examples/complex.prc."""
+    """tests/golden/scenes/complex_c5.npz (tools/make_c5_fixture.py) against a fresh load of examples/complex.prc (counts and sha256 digests
+    of its arrays, recorded by tools/make_reference_goldens.py)."""
     path = os.path.join(HERE, "golden", "scenes", "complex_c5.npz")
     fx = scene.ArrayScene(path)   # the sky table is rebuilt from the stored sun position, turbidity and ground albedo
     assert (fx.desc.n_triangles, fx.desc.n_entities, fx.desc.n_materials, fx.desc.n_lights) == (304046, 68, 6, 2)
     sky = [fx.desc.lights[i] for i in range(fx.desc.n_lights) if fx.desc.lights[i].kind == abi.LIGHT_SKY][0]
     table = fx.tables[sky.table_offset:sky.table_offset + 256 * 512 * 11]
     assert np.isfinite(table).all() and table.min() >= 0 and 0.1 < table.max() < 1.0   # W / (m^2 sr nm): the circumsolar peak of a clear sky
-    if not os.path.isdir(REF_EXAMPLES):
-        return
-    ref = scene.PrcScene(path=os.path.join(REF_EXAMPLES, "complex.prc"))   # loads as shipped: no host-supplied table
-    rsky = [ref.desc.lights[i] for i in range(ref.desc.n_lights) if ref.desc.lights[i].kind == abi.LIGHT_SKY][0]
-    assert np.array_equal(arr(ref.desc.spectral_tables, ref.desc.n_spectral_table_values, np.float32)[rsky.table_offset:rsky.table_offset + 256 * 512 * 11], table)
+    ref = REF_GOLDEN["complex"]   # loaded as shipped: no host-supplied table
+    sha = lambda b: hashlib.sha256(b).hexdigest()   # noqa: E731
+    assert sha(np.ascontiguousarray(table, dtype=np.float32).tobytes()) == ref["sky_table"]
     for f in ("n_vertices", "n_triangles", "n_entities", "n_materials", "n_spectra", "n_lights"):
-        assert getattr(fx.desc, f) == getattr(ref.desc, f), f
-    assert np.array_equal(arr(fx.desc.positions, 3 * fx.desc.n_vertices, np.float32), arr(ref.desc.positions, 3 * ref.desc.n_vertices, np.float32))
-    assert np.array_equal(arr(fx.desc.indices, 3 * fx.desc.n_triangles, np.uint32), arr(ref.desc.indices, 3 * ref.desc.n_triangles, np.uint32))
-    for i in range(fx.desc.n_materials):
-        assert struct_bytes(fx.desc.materials[i]) == struct_bytes(ref.desc.materials[i])
+        assert getattr(fx.desc, f) == ref[f], f
+    assert sha(arr(fx.desc.positions, 3 * fx.desc.n_vertices, np.float32).tobytes()) == ref["positions"]
+    assert sha(arr(fx.desc.indices, 3 * fx.desc.n_triangles, np.uint32).tobytes()) == ref["indices"]
+    assert [sha(struct_bytes(fx.desc.materials[i])) for i in range(fx.desc.n_materials)] == ref["materials"]
 
 
 EMBED = """(scene :render_width 8 :render_height 8
@@ -559,17 +556,19 @@ def test_spd_file_node_reads_csv_like_the_reference(tmp_path):
             _spd_scene(tmp_path, text, expr)
 
 
-def test_reference_uv_light_spectrum_loads():
-    path = os.path.join(REF_EXAMPLES, "UVLight.csv") if "REF_EXAMPLES" in globals() else "/root/reference/examples/UVLight.csv"
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present")
+def test_reference_uv_light_spectrum_loads(tmp_path):
+    """examples/UVLight.csv as the loader read it (tools/make_reference_goldens.py), written back as a CSV and read again."""
+    uv = REF_GOLDEN["uv_light"]
+    step = (uv["wl_end"] - uv["wl_start"]) / (len(uv["values"]) - 1)
+    (tmp_path / "UVLight.csv").write_text("".join("%.9g,%.9g\n" % (uv["wl_start"] + i * step, v) for i, v in enumerate(uv["values"])))
     src = "(scene (camera :name 'c' :type 'standard') (emission :name 'e' :type 'standard' :radiance (smul (spd 'UVLight.csv') 100)) (material :name 'm' :type 'diffuse'))"
-    s = scene.PrcScene(source=src, include_dir=os.path.dirname(path))            # cornellbox_fluorescent.prc:56
+    s = scene.PrcScene(source=src, include_dir=str(tmp_path))            # cornellbox_fluorescent.prc:56
     mul = s.desc.spectra[s.desc.emissions[0].radiance]
     assert mul.kind == abi.SPEC_MUL
     sp = s.desc.spectra[mul.lhs] if s.desc.spectra[mul.lhs].kind == abi.SPEC_TABLE else s.desc.spectra[mul.rhs]
     v = np.array([s.desc.spectral_tables[sp.table_offset + i] for i in range(sp.table_count)])
     assert (sp.table_count, sp.wl_start, sp.wl_end) == (111, 300.0, 410.0) and v.max() > 0 and (v >= 0).all() and 340 < 300 + v.argmax() < 380
+    assert np.array_equal(v.astype(np.float32), np.array(uv["values"], dtype=np.float32))
 
 
 def test_every_reference_illuminant_is_available():

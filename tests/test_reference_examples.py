@@ -1,8 +1,11 @@
 """Every reference example the loader accepts (17 of examples/*.prc next to complex.prc = BASELINE config C5, which has its own fixture and tests; `vcm` / `ao` integrators replaced by `direct`), reduced to array
 fixtures by tools/make_example_fixtures.py (the reference's files do not travel to the GPU box): the HIP path renders each one and is
 compared with the checker -- hit ids, sample / feedback planes and statistics exact, XYZ bit for bit where the pixel filter has a single
-live tap.  CPU: the fixtures are current (equal to a fresh conversion where the reference checkout exists) and the checker renders them."""
+live tap.  CPU: the fixtures are current (equal to a fresh conversion: golden/reference_examples.json holds its digests,
+tools/make_reference_goldens.py) and the checker renders them."""
 import glob
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -15,7 +18,6 @@ import oracle_binding as ob
 HERE = os.path.dirname(os.path.abspath(__file__))
 FIXTURES = sorted(glob.glob(os.path.join(HERE, "golden", "scenes", "examples", "*.npz")))
 NAMES = [os.path.basename(f)[:-4] for f in FIXTURES]
-REF_EXAMPLES = "/root/reference/examples"
 
 
 def load(path):
@@ -29,29 +31,14 @@ def single_tap(sc):
 
 def test_there_is_a_fixture_for_every_example_the_loader_accepts():
     assert len(FIXTURES) == 17 and "cornellbox" in NAMES and "material_showcase" in NAMES and "skylens" in NAMES
-    if not os.path.isdir(REF_EXAMPLES):
-        pytest.skip("reference checkout not present")
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
-    import make_example_fixtures as mk
-    accepted = []
-    for f in sorted(glob.glob(os.path.join(REF_EXAMPLES, "*.prc"))):
-        name = os.path.basename(f)
-        if name in mk.SKIP:
-            continue
-        try:
-            s = mk.load(f)
-        except abi.PrgpuError:
-            continue
-        accepted.append(name[:-4])
-        import tempfile
-        with tempfile.TemporaryDirectory() as d:          # the committed fixture is what the loader produces today
-            p = os.path.join(d, "x.npz")
-            scene.save_scene_npz(p, s.desc, sky_params=s.sky_params())
-            a, b = np.load(p), np.load(os.path.join(HERE, "golden", "scenes", "examples", name[:-4] + ".npz"))
-            assert sorted(a.files) == sorted(b.files), name
-            for k in a.files:
-                assert np.array_equal(a[k], b[k]), (name, k)
+    with open(os.path.join(HERE, "golden", "reference_examples.json")) as f:
+        fresh = json.load(f)["fixture_digests"]   # every array of a fresh conversion of each example the fixture tool accepts
+    accepted = sorted(fresh)
+    for name in accepted:                          # the committed fixture is what the loader produced
+        b = np.load(os.path.join(HERE, "golden", "scenes", "examples", name + ".npz"))
+        assert sorted(fresh[name]) == sorted(b.files), name
+        for k in b.files:
+            assert hashlib.sha256(np.ascontiguousarray(b[k]).tobytes()).hexdigest() == fresh[name][k], (name, k)
     assert accepted == NAMES
 
 

@@ -13,7 +13,7 @@ for E in "$@"; do
   if [ "$E" != "$L" ]; then export "${E#*@}"; fi
   if [ "$L" = "default" ]; then unset PRGPU_LIBRARY; else export PRGPU_LIBRARY=$R/pearray_amd/csrc/libprgpu_$L.so; fi
   for W in $WL; do
-    LINE=$(timeout -k 10 300 python3 $R/bench.py --workload $W --steps 32 --warmup 8 --no-cpu-baseline 2>>"$OUT/$TAG.err" | tail -1)
+    LINE=$(timeout -k 10 300 python3 $R/bench.py --workload $W --steps 32 --warmup 8 --full --no-cpu-baseline 2>>"$OUT/$TAG.err" | tail -1)
     if [ -z "$LINE" ]; then   # the run died (a faulting kernel, a timeout): nothing else is started on this GPU in this call
       echo "$L $W FAILED: see $TAG.err; stopping" | tee -a "$OUT/$TAG.log"; exit 1
     fi

@@ -9,6 +9,6 @@ mkdir -p "$OUT"
 : > "$OUT/$TAG.log"
 for S in "$@"; do
   if [ "$S" = "-" ]; then E=""; else E="$S"; fi
-  LINE=$(env $E timeout -k 10 300 python3 $R/bench.py --workload $W --steps 24 --warmup 8 --no-cpu-baseline 2>>"$OUT/$TAG.err" | tail -1)
+  LINE=$(env $E timeout -k 10 300 python3 $R/bench.py --workload $W --steps 24 --warmup 8 --full --no-cpu-baseline 2>>"$OUT/$TAG.err" | tail -1)
   echo "[$S] $(echo "$LINE" | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); r=d.get("roofline",{}); print(d["value"], d["ms_per_step"], r.get("lane_utilisation"), r.get("shade_pass_fill"))' 2>/dev/null)" | tee -a "$OUT/$TAG.log"
 done
