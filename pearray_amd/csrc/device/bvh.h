@@ -15,6 +15,8 @@ struct BvhBuildInput {
 	const uint8_t* tri_class = nullptr; // device, or null: per-triangle material class, copied into the leaf records (float 31: one byte per slot)
 	uint32_t stack_capacity = 0xFFFFFFFFu; // entries a traversal stack holds (render.h, trace_stack_capacity): a tree whose deepest walk needs more is refused
 	int width = 0; // children per inner record: 4 (a record = a radix node at even depth and its grandchildren), 6 (greedy collapse by surface area), 0 = the one that costs less (bvh.hip)
+	int top = -1; // the top of the tree (BvhBuildOutput::top): 0, 1 or 2 builds that order only, -1 = all three are priced and the cheapest is kept; a scene of one entity has no top to choose (0 is built)
+	int parity = -1; // the four-wide collapse: 0 = records at even depths of the radix tree, 1 = at odd depths, -1 = the one whose estimate is lower among those that fit the stack
 };
 struct BvhBuildOutput {
 	Rec64* recs = nullptr; // device, addressed in 64-byte units: unit 0 is the root inner record; from unit 2 on the child groups of the

@@ -948,8 +948,9 @@ bool build_lbvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream
 				HIPC(hipMalloc(&front_count, sizeof(uint32_t)));
 			}
 		}
-		const int n_orders = (n > 3 && in.n_entities > 1) ? 3 : 1;
-		for (int pass = 0, order = 0;; ++pass) {
+		const bool top_forced = in.top >= 0 && in.top <= 2 && n > 3 && in.n_entities > 1; // (a forced top builds that order only)
+		const int n_orders	  = (n > 3 && in.n_entities > 1 && !top_forced) ? 3 : 1;
+		for (int pass = 0, order = top_forced ? in.top : 0;; ++pass) {
 			HIPC(hipMemcpyAsync(entity_rank, codes[order].data(), codes[order].size() * 4, hipMemcpyHostToDevice, stream));
 			hipLaunchKernelGGL(k_morton, dim3(G), dim3(B), 0, stream, n, wv, in.tri_entity, ebounds, entity_rank, keys, vals);
 			HIPC(hipGetLastError());
@@ -1008,8 +1009,14 @@ bool build_lbvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream
 				// (C4: 3.9 % more inner records per ray with the wrong one), so both are priced
 				const uint32_t bound_even = 3u * (bounds_host[0] + 1u), bound_odd = 3u * (bounds_host[1] + 1u), bound6 = bounds_host[2];
 				const bool fit_even = bound_even <= in.stack_capacity, fit_odd = bound_odd <= in.stack_capacity;
-				const bool odd = fit_odd && (!fit_even || sums[1] < sums[0]);
+				// (a forced parity is taken whether it fits or not: a tree that does not fit is refused, as for a forced width)
+				const bool odd = in.parity >= 0 ? in.parity == 1 : fit_odd && (!fit_even || sums[1] < sums[0]);
 				const uint32_t bound4 = odd ? bound_odd : bound_even;
+				if (in.parity >= 0 && in.width != 6 && bound4 > in.stack_capacity) { // (not left to `auto`'s way out, the six-wide tree: the caller asked for THIS tree)
+					err = "the four-wide BVH of the forced parity is " + std::to_string(bound4) + " stack entries deep in the worst case, the traversal stack holds "
+						  + std::to_string(in.stack_capacity);
+					goto done;
+				}
 				if (odd) {
 					width = -1;
 					std::swap(inner_flag, odd_flag);
@@ -1038,6 +1045,8 @@ bool build_lbvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream
 				}
 				if (pass == 0)
 					first_cost = cost;
+				if (top_forced)
+					break;
 				if (pass + 1 < n_orders) {
 					order = pass + 1;
 					continue;

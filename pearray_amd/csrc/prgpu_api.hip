@@ -69,6 +69,11 @@ struct Knobs {
 	const char* dump_block_life = nullptr; // PRGPU_DUMP_BLOCK_LIFE=<file>: per-block lifetimes of the last instrumented launch
 	int bvh_width			   = 0;		  // PRGPU_BVH_WIDTH=auto|4|6: children per inner BVH record (0 = auto: the tree whose estimated cost is lower, device/bvh.hip)
 	bool bvh_width_invalid	   = false;
+	int bvh_top				   = -1;	  // PRGPU_BVH_TOP=auto|file|area|morton: the order of the entities at the top of the tree (0 / 1 / 2; -1 = auto: all three are built, the cheapest
+										  // is kept).  A scene of one entity has no top to choose: prgpu_pipeline_info's bvh_top says what was built.
+	int bvh_parity			   = -1;	  // PRGPU_BVH_PARITY=auto|even|odd: which depths of the radix tree become four-wide records (0 / 1; -1 = auto: the cheaper one that fits the stack).
+										  // Test aids: the trees `auto` would not pick for a scene are walked on purpose (tests/test_gpu_bvh_width.py); no effect on a six-wide tree.
+	bool bvh_top_invalid = false, bvh_parity_invalid = false;
 	int trace_ranges		   = -1;	  // PRGPU_TRACE_RANGES=1: load the roctx library for the named ranges even when no profiler brought it along; 0: never emit ranges
 };
 Knobs read_knobs()
@@ -89,6 +94,14 @@ Knobs read_knobs()
 	if (const char* env = getenv("PRGPU_BVH_WIDTH")) {
 		k.bvh_width			= std::strcmp(env, "auto") == 0 ? 0 : (std::strcmp(env, "4") == 0 ? 4 : (std::strcmp(env, "6") == 0 ? 6 : -1));
 		k.bvh_width_invalid = k.bvh_width < 0;
+	}
+	if (const char* env = getenv("PRGPU_BVH_TOP")) {
+		k.bvh_top		  = std::strcmp(env, "auto") == 0 ? -1 : (std::strcmp(env, "file") == 0 ? 0 : (std::strcmp(env, "area") == 0 ? 1 : (std::strcmp(env, "morton") == 0 ? 2 : -2)));
+		k.bvh_top_invalid = k.bvh_top < -1;
+	}
+	if (const char* env = getenv("PRGPU_BVH_PARITY")) {
+		k.bvh_parity		 = std::strcmp(env, "auto") == 0 ? -1 : (std::strcmp(env, "even") == 0 ? 0 : (std::strcmp(env, "odd") == 0 ? 1 : -2));
+		k.bvh_parity_invalid = k.bvh_parity < -1;
 	}
 	k.pl.slots_per_wave	  = (uint32_t)num("PRGPU_PL_SLOTS", k.pl.slots_per_wave, 64, 256);
 	k.pl.shade_min		  = (int)num("PRGPU_PL_SHADE_MIN", k.pl.shade_min, 1, 64);
@@ -572,7 +585,13 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 	prd::BvhBuildInput bin{ d->n_triangles, d->n_entities, sc.positions, sc.indices, sc.tri_entity, sc.entities, sc.tri_class };
 	if (s->knobs.bvh_width_invalid)
 		return fail(PRGPU_EINVAL, "PRGPU_BVH_WIDTH must be auto, 4 or 6");
+	if (s->knobs.bvh_top_invalid)
+		return fail(PRGPU_EINVAL, "PRGPU_BVH_TOP must be auto, file, area or morton");
+	if (s->knobs.bvh_parity_invalid)
+		return fail(PRGPU_EINVAL, "PRGPU_BVH_PARITY must be auto, even or odd");
 	bin.width = s->knobs.bvh_width;
+	bin.top	  = s->knobs.bvh_top;
+	bin.parity = s->knobs.bvh_parity;
 	bin.stack_capacity = prd::trace_stack_capacity();
 	prd::BvhBuildOutput bout;
 	{
