@@ -424,7 +424,7 @@ int  prgpu_download_primary_hits(prgpu_scene* s, uint32_t* entity, uint32_t* pri
 /* Time the traversal kernels alone on the rays recorded during the last iteration is not part of the
  * ABI; bench.py measures kernels with HIP events through prgpu_kernel_time_ms(). */
 /* Accumulated HIP-event time [ms] and launch count of a named kernel family since scene creation
- * ("trace_closest", "trace_any", "shade", "raygen", "resolve", "sort"). Requires prgpu_set_timing(s,1). */
+ * ("trace_closest", "trace_any", "shade", "raygen", "resolve", "sort", "path", "reduce", "ao"). Requires prgpu_set_timing(s,1). */
 int  prgpu_set_timing(prgpu_scene* s, int enabled);
 int  prgpu_kernel_time_ms(prgpu_scene* s, const char* family, double* total_ms, uint64_t* launches);
 
@@ -500,6 +500,25 @@ int prgpu_lpe_match(const char* expression, const uint8_t* symbols, uint32_t cou
 int prgpu_enable_lpe(prgpu_scene* s, uint32_t n, const char* const* expressions);
 int prgpu_download_lpe(prgpu_scene* s, uint32_t index, float* xyz); /* W*H*3 fp32 */
 
+/* -- ambient occlusion integrator -------------------------------------------------------------
+ * IntAOInstance (src/plugins/main/integrators/ambientocclusion.cpp:29-74; `(integrator :type 'ao'|'occlusion'|'ambient_occlusion'
+ * :sample_count N)`): per camera sample that hits a surface, N occlusion rays over the uniform hemisphere around the shading normal,
+ * drawn from the pixel's generator, and one fragment of radiance 1 - occluded / N at unit importance; a miss adds nothing.  Materials,
+ * emissions and lights play no part.  Enable before the first iteration (PRGPU_EINVAL afterwards, and for sample_count == 0 or a film
+ * with 2^32 or more rays per iteration).  From then on prgpu_render runs an iteration-synchronous pipeline of its own for every pixel
+ * filter, whatever PRGPU_MODE says (prgpu_pipeline_info reports mode 0); tiles, AOVs, the variance planes, the reduce and the statistics
+ * (shadow rays = hits * N, no bounce rays) work as for `direct`.  Light path expressions are not provided with it: prgpu_enable_lpe
+ * -- and prgpu_outputs_enable with an :lpe channel -- return PRGPU_EUNSUPPORTED on such a scene, and it refuses a scene that has them.
+ * With prgpu_set_timing the occlusion kernel is the kernel family "ao". */
+int prgpu_enable_ambient_occlusion(prgpu_scene* s, uint32_t sample_count);
+/* Occluded rays per pixel, summed over all iterations so far (W*H u32). */
+int prgpu_download_ao_counts(prgpu_scene* s, uint32_t* occluded);
+/* Debug record of the LAST iteration, kept only while prgpu_set_instrumentation(s, 1) is on (PRGPU_EINVAL otherwise, and before the first
+ * instrumented iteration): per pixel the generator state before the first occlusion draw (W*H u64), per pixel and sample the ray's
+ * origin and direction (W*H*N*3 floats each) and whether it was occluded (W*H*N bytes).  Pixels whose camera ray missed hold state 0
+ * and all-zero rays.  Any pointer may be NULL. */
+int prgpu_download_ao_samples(prgpu_scene* s, uint64_t* rng_state, float* org, float* dir, uint8_t* occluded);
+
 /* Scheduling statistic of the persistent pipeline: path vertices traced per pixel so far (W*H u32; kept only while every owned pixel is in
  * flight at once -- a small tile share --, 0 otherwise and in the other pipelines).  The
  * backend uses it to hand the pixels with the longest sample chains to the fastest blocks of a small tile share; exposed for
@@ -555,7 +574,7 @@ int prgpu_write_exr(const char* path, uint32_t width, uint32_t height, uint32_t 
 /* -- .prc scene files ---------------------------------------------------------------------
  * Replaces SceneLoader::loadFromFile / loadFromString (src/loader/SceneLoader.cpp:44-72) for the part of the scene language the
  * `direct` hot path evaluates: (scene :render_width :render_height :camera :spectral_domain :spectral_hero), (sampler), (filter),
- * (spectral_mapper), (integrator :type 'direct'), (camera :type 'standard'), (material :type 'diffuse'), (emission :type 'standard'),
+ * (spectral_mapper), (integrator :type 'direct'|'ao'), (camera :type 'standard'), (material :type 'diffuse'), (emission :type 'standard'),
  * spectral expressions number / (refl r g b) / (illum r g b) / (illuminant "D65") / (spectrum :start :end v...) / (smul a b),
  * inline (mesh (attribute :type 'p'|'n' ...) (faces ...) (materials ...)), (entity :type 'mesh' ...), (include "file"),
  * (light :type 'env'|'distant'|'sun'|'sky') -- the sky's Hosek-Wilkie table is built by the loader (prgpu_sky_table).
@@ -573,7 +592,7 @@ typedef struct prgpu_prc_sky {
 typedef struct prgpu_prc_options {
 	uint32_t width, height; /* 0: keep :render_width / :render_height */
 	uint32_t aa_samples;    /* 0: keep the aa sampler's :sample_count */
-	uint32_t force_direct;  /* 1: accept any (integrator :type ...) and render it with `direct` at default parameters */
+	uint32_t force_direct;  /* 1: accept any (integrator :type ...) and render it with `direct` at default parameters (`ao` included) */
 	uint64_t seed;          /* 0: RenderSettings default (42) */
 	uint32_t n_skies;       /* host-supplied sky tables (may be 0: the loader builds them) */
 	uint32_t reserved;
@@ -602,6 +621,11 @@ int prgpu_prc_load_file(const char* path, const prgpu_prc_options* options, prgp
 int prgpu_prc_load_string(const char* source, const char* include_dir, const prgpu_prc_options* options, prgpu_prc** out);
 const prgpu_scene_desc* prgpu_prc_desc(const prgpu_prc* scene);
 const char* prgpu_prc_warnings(const prgpu_prc* scene); /* newline separated */
+/* The scene's (integrator ...) block: PRGPU_INTEGRATOR_DIRECT (also without a block, and for every type under force_direct) or
+ * PRGPU_INTEGRATOR_AO with its :sample_count (default 10; 0 for `direct`).  A host renders an AO scene by calling
+ * prgpu_enable_ambient_occlusion(scene, ao_sample_count) after prgpu_scene_create.  Either output pointer may be NULL. */
+enum { PRGPU_INTEGRATOR_DIRECT = 0, PRGPU_INTEGRATOR_AO = 1 };
+int prgpu_prc_integrator(const prgpu_prc* scene, uint32_t* kind, uint32_t* ao_sample_count);
 /* What the SkyModel of light `light` (a PRGPU_LIGHT_SKY of the loaded scene) was built from; PRGPU_EINVAL for any other light. */
 int prgpu_prc_sky_info(const prgpu_prc* scene, uint32_t light, prgpu_sky_params* out);
 /* The scene's (output ...) blocks: their channels (all files, in file order) and the :name of file k (NULL beyond the last). */

@@ -32,6 +32,7 @@ SAMPLER_RANDOM, SAMPLER_MJITT, SAMPLER_SOBOL, SAMPLER_HALTON, SAMPLER_HAMMERSLEY
 MAPPER_SPD_CMIS, MAPPER_RANDOM, MAPPER_SPD_HERO, MAPPER_CIE, MAPPER_CIE_Y, MAPPER_AGH_CMIS, MAPPER_AGH_HERO = range(7)
 FILTER_BLOCK, FILTER_TRIANGLE, FILTER_GAUSSIAN, FILTER_MITCHELL, FILTER_LANCZOS = range(5)
 MIS_BALANCE, MIS_POWER = range(2)
+INTEGRATOR_DIRECT, INTEGRATOR_AO = range(2)
 
 STAT_NAMES = ("camera_rays", "light_rays", "primary_rays", "bounce_rays", "shadow_rays", "monochrome_rays",
               "pixel_samples", "entity_hits", "background_hits", "camera_depth", "light_depth")
@@ -193,6 +194,9 @@ SYMBOLS = {
     "prgpu_enable_variance": (C.c_int, [_VP]),
     "prgpu_download_variance": (C.c_int, [_VP, _F32P, _F32P]),
     "prgpu_path_cost": (C.c_int, [_VP, _U32P]),
+    "prgpu_enable_ambient_occlusion": (C.c_int, [_VP, C.c_uint32]),
+    "prgpu_download_ao_counts": (C.c_int, [_VP, _U32P]),
+    "prgpu_download_ao_samples": (C.c_int, [_VP, _U64P, _F32P, _F32P, _U8P]),
     "prgpu_lpe_check": (C.c_int, [C.c_char_p]),
     "prgpu_lpe_match": (C.c_int, [C.c_char_p, _U8P, C.c_uint32]),
     "prgpu_enable_lpe": (C.c_int, [_VP, C.c_uint32, C.POINTER(C.c_char_p)]),
@@ -216,6 +220,7 @@ SYMBOLS = {
     "prgpu_prc_load_string": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(PrcOptions), C.POINTER(_VP)]),
     "prgpu_prc_desc": (C.POINTER(SceneDesc), [_VP]),
     "prgpu_prc_warnings": (C.c_char_p, [_VP]),
+    "prgpu_prc_integrator": (C.c_int, [_VP, _U32P, _U32P]),
     "prgpu_prc_last_error": (C.c_char_p, []),
     "prgpu_prc_free": (None, [_VP]),
 }

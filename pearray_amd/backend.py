@@ -32,6 +32,9 @@ class RenderContext:
         abi.check(self.lib.prgpu_scene_create(C.byref(scene.desc), int(device), C.byref(self._h)))
         self.width, self.height = scene.width, scene.height
         self.iterations_done = 0
+        self.ao_sample_count = 0
+        if getattr(scene, "integrator", abi.INTEGRATOR_DIRECT) == abi.INTEGRATOR_AO:   # (integrator :type 'ao') / SceneBuilder.ambient_occlusion
+            self.enableAmbientOcclusion(scene.ao_sample_count)
 
     def close(self):
         if self._h:
@@ -150,6 +153,31 @@ class RenderContext:
         out = np.empty(self.width * self.height * 3, dtype=np.float32)
         abi.check(self.lib.prgpu_download_lpe(self._h, int(index), _f32p(out)))
         return out.reshape(self.height, self.width, 3)
+
+    def enableAmbientOcclusion(self, sample_count):
+        """Render with the ambient occlusion integrator (ambientocclusion.cpp:29-74) instead of `direct`: `sample_count` occlusion rays
+        per camera sample that hits a surface; enable before the first iteration."""
+        abi.check(self.lib.prgpu_enable_ambient_occlusion(self._h, int(sample_count)))
+        self.ao_sample_count = int(sample_count)
+
+    def aoCounts(self):
+        """Occluded rays per pixel over all iterations so far, uint32 [H, W]."""
+        out = np.empty(self.width * self.height, dtype=np.uint32)
+        abi.check(self.lib.prgpu_download_ao_counts(self._h, _u32p(out)))
+        return out.reshape(self.height, self.width)
+
+    def aoSamples(self):
+        """The occlusion rays of the LAST iteration (instrumentation must be on): (state uint64 [H, W] -- the pixel's generator before
+        its first occlusion draw, 0 where the camera ray missed --, origin float32 [H, W, N, 3], direction float32 [H, W, N, 3],
+        occluded bool [H, W, N])."""
+        n, k = self.width * self.height, self.ao_sample_count
+        state = np.empty(n, dtype=np.uint64)
+        org, direction = np.empty(n * k * 3, dtype=np.float32), np.empty(n * k * 3, dtype=np.float32)
+        occ = np.empty(n * k, dtype=np.uint8)
+        abi.check(self.lib.prgpu_download_ao_samples(self._h, state.ctypes.data_as(C.POINTER(C.c_uint64)), _f32p(org), _f32p(direction),
+                                                     occ.ctypes.data_as(C.POINTER(C.c_uint8))))
+        shape = (self.height, self.width, k)
+        return state.reshape(self.height, self.width), org.reshape(shape + (3,)), direction.reshape(shape + (3,)), occ.reshape(shape).astype(bool)
 
     def pathCost(self):
         """Path vertices traced per pixel so far (persistent pipeline; scheduling statistic)."""

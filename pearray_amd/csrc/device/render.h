@@ -90,4 +90,27 @@ void launch_service_closest_split(const DevScene& sc, uint32_t n, const float* o
 								  unsigned long long* gstats, hipStream_t st); // prototype, see render.hip
 void launch_service_any(const DevScene& sc, uint32_t n, const float* org, const float* dir, const float* tmin, const float* distance,
 						uint8_t* occluded, const TraceWorkspace& ws, unsigned long long* gstats, hipStream_t st);
+// What prgpu_enable_ambient_occlusion allocates; passed by value.
+struct AoState {
+	float4* rec;			// 4 per hit: (P, slot bits), (N, state low), (Nx, state high), (Ny, 0)
+	uint32_t* occluded;		// per hit: occluded rays of this iteration
+	const uint64_t* jump;	// PCG_MULT^(2 k), k < sample_count
+	uint32_t* counts;		// per pixel: occluded rays over all iterations (prgpu_download_ao_counts)
+	uint64_t jump_all;		// PCG_MULT^(2 sample_count)
+	uint32_t sample_count;
+	// debug record of the last iteration (instrumented kernels only; cleared before every iteration): per pixel the generator state, per pixel and sample the ray
+	uint64_t* dbg_state;
+	float* dbg_org;
+	float* dbg_dir;
+	uint8_t* dbg_occluded;
+};
+
+// Ambient occlusion pipeline (device/ao.inl): the three passes between k_trace_closest and k_resolve of an iteration.  `n_hits` is the device
+// counter the closest-hit launch zeroes (its shade_counters[0]); no pass needs it on the host.  instrumented: traversal counters + ray dump.
+void launch_ao_hits(const DevScene& sc, const PathState& ps, const AoState& ao, uint32_t n_slots, bool instrumented, uint32_t* n_hits, uint32_t* queue_head_closest,
+					uint32_t* queue_head_ao, unsigned long long* gstats, hipStream_t st);
+void launch_ao_occlusion(const DevScene& sc, const PathState& ps, const AoState& ao, uint32_t n_slots, bool instrumented, const uint32_t* n_hits, const TraceWorkspace& ws,
+						 unsigned long long* gstats, hipStream_t st);
+void launch_ao_splat(const DevScene& sc, const PathState& ps, const AoState& ao, uint32_t n_slots, const uint32_t* n_hits, hipStream_t st);
+bool ao_counts_folded(); // how the occlusion kernel was built (PR_AO_FOLD): one atomic per hit and wave step, or one per occluded ray
 } // namespace prd

@@ -2937,6 +2937,8 @@ __global__ void __launch_bounds__(TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu
 #include "path_wave.inl"
 
 #if PR_TU == 0
+#include "ao.inl"
+
 // ---- ray service kernels (IArchive surface) ------------------------------------------------------------
 __global__ void __launch_bounds__(TRAV_BLOCK) k_service_closest(DevScene sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,
 															   const float* __restrict__ tmin_a, const float* __restrict__ tmax_a, uint32_t* entity,
@@ -3367,6 +3369,28 @@ void launch_service_any(const DevScene& sc, uint32_t n, const float* org, const 
 	hipLaunchKernelGGL(k_service_any, trav_grid(ws, n), dim3(TRAV_BLOCK), 0, st, sc, n, org, dir, tmin, distance, occluded, ws.queue_head, ws.spill,
 					   ws.refill_below, gstats);
 }
+void launch_ao_hits(const DevScene& sc, const PathState& ps, const AoState& ao, uint32_t n_slots, bool instrumented, uint32_t* n_hits, uint32_t* queue_head_closest,
+					uint32_t* queue_head_ao, unsigned long long* gstats, hipStream_t st)
+{
+	if (instrumented)
+		hipLaunchKernelGGL(k_ao_hits<true>, grid_for(n_slots), dim3(256), 0, st, sc, ps, ao, n_slots, n_hits, queue_head_closest, queue_head_ao, gstats);
+	else
+		hipLaunchKernelGGL(k_ao_hits<false>, grid_for(n_slots), dim3(256), 0, st, sc, ps, ao, n_slots, n_hits, queue_head_closest, queue_head_ao, gstats);
+}
+void launch_ao_occlusion(const DevScene& sc, const PathState& ps, const AoState& ao, uint32_t n_slots, bool instrumented, const uint32_t* n_hits, const TraceWorkspace& ws,
+						 unsigned long long* gstats, hipStream_t st)
+{
+	const dim3 g = trav_grid(ws, n_slots * ao.sample_count); // (every owned pixel may hit; blocks that find the queue empty leave at once)
+	if (instrumented)
+		hipLaunchKernelGGL(k_ao_occlusion<true>, g, dim3(TRAV_BLOCK), 0, st, sc, ps, ao, n_hits, ws.queue_head, ws.spill, ws.refill_below, gstats);
+	else
+		hipLaunchKernelGGL(k_ao_occlusion<false>, g, dim3(TRAV_BLOCK), 0, st, sc, ps, ao, n_hits, ws.queue_head, ws.spill, ws.refill_below, gstats);
+}
+void launch_ao_splat(const DevScene& sc, const PathState& ps, const AoState& ao, uint32_t n_slots, const uint32_t* n_hits, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_ao_splat, grid_for(n_slots), dim3(256), 0, st, sc, ps, ao, n_hits);
+}
+bool ao_counts_folded() { return PR_AO_FOLD != 0; }
 
 #endif // PR_TU == 0
 

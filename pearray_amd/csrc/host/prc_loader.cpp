@@ -49,6 +49,7 @@ struct prgpu_prc {
 	std::vector<std::string> output_names;
 	prgpu_scene_desc desc;
 	std::string warnings;
+	uint32_t integrator = PRGPU_INTEGRATOR_DIRECT, ao_sample_count = 0;
 };
 
 namespace {
@@ -657,13 +658,24 @@ struct Loader {
 	{
 		const std::string type = lower(get_string(g, "type", ""));
 		const bool direct	   = type == "direct" || type == "standard" || type == "default";
+		if ((type == "ao" || type == "occlusion" || type == "ambient_occlusion") && !opt.force_direct) { // ambientocclusion.cpp:107,124
+			const double n = get_number(g, "sample_count", 10);
+			if (!(n >= 1 && n <= 4294967295.0))
+				fail(PRGPU_EINVAL, where(g) + ": :sample_count must be a positive integer");
+			out.integrator		= PRGPU_INTEGRATOR_AO;
+			out.ao_sample_count = (uint32_t)n;
+			have_integrator		= true; // (the `direct` parameters keep their defaults: nothing reads them)
+			return;
+		}
 		if (!direct && !opt.force_direct)
-			fail(PRGPU_EUNSUPPORTED, where(g) + ": integrator '" + type + "' is not supported (only direct/standard/default; set force_direct to render with it anyway)");
+			fail(PRGPU_EUNSUPPORTED, where(g) + ": integrator '" + type + "' is not supported (only direct/standard/default and ao/occlusion/ambient_occlusion; set force_direct to render with `direct` anyway)");
 		if (!direct) {
 			warn(where(g) + ": integrator '" + type + "' replaced by 'direct' with default parameters (force_direct)");
 			have_integrator = true;
 			return;
 		}
+		out.integrator		= PRGPU_INTEGRATOR_DIRECT; // (a later block replaces an earlier one)
+		out.ao_sample_count = 0;
 		settings.max_ray_depth		= (uint32_t)get_number(g, "max_ray_depth", settings.max_ray_depth);
 		settings.soft_max_ray_depth = std::min(settings.max_ray_depth, (uint32_t)get_number(g, "soft_max_ray_depth", settings.soft_max_ray_depth));
 		const std::string mis		= lower(get_string(g, "mis", "balance"));
@@ -2045,6 +2057,16 @@ int prgpu_prc_load_file(const char* path, const prgpu_prc_options* opt, prgpu_pr
 
 const prgpu_scene_desc* prgpu_prc_desc(const prgpu_prc* p) { return p ? &p->desc : nullptr; }
 const char* prgpu_prc_warnings(const prgpu_prc* p) { return p ? p->warnings.c_str() : ""; }
+int prgpu_prc_integrator(const prgpu_prc* p, uint32_t* kind, uint32_t* ao_sample_count)
+{
+	if (!p)
+		return PRGPU_EINVAL;
+	if (kind)
+		*kind = p->integrator;
+	if (ao_sample_count)
+		*ao_sample_count = p->ao_sample_count;
+	return PRGPU_OK;
+}
 int prgpu_prc_sky_info(const prgpu_prc* p, uint32_t light, prgpu_sky_params* out)
 {
 	if (!p || !out || light >= p->lights.size() || p->lights[light].kind != PRGPU_LIGHT_SKY || light >= p->sky_params.size())

@@ -180,8 +180,8 @@ struct TimedLaunch {
 	hipEvent_t start, stop;
 	int family;
 };
-const char* const FAMILY_NAMES[] = { "raygen", "trace_closest", "shade", "trace_any", "resolve", "sort", "path", "reduce" };
-constexpr int N_FAMILIES		 = 8;
+const char* const FAMILY_NAMES[] = { "raygen", "trace_closest", "shade", "trace_any", "resolve", "sort", "path", "reduce", "ao" };
+constexpr int N_FAMILIES		 = 9;
 
 } // namespace
 
@@ -247,6 +247,11 @@ struct prgpu_scene {
 	uint64_t family_launches[N_FAMILIES] = { 0 };
 	uint64_t rays_closest = 0, rays_any = 0;
 	uint32_t next_iteration = 0;
+	// ambient occlusion integrator (prgpu_enable_ambient_occlusion; device/ao.inl): its pipeline replaces the scene's mode for good
+	bool ao_enabled = false;
+	prd::AoState ao{};
+	prd::TraceWorkspace ws_ao;		  // the occlusion launch: the ray service's grid
+	std::vector<prgpu_tile> tiles;	  // as last given to apply_tiles (enabling AO orders the owned pixels again: the order depends on the mode)
 	prd::DevLpe lpe_host{}; // host copy of the light path expression block (plane pointers for downloads and the reduce)
 	uint32_t order_tuned_at = 0; // iteration count the pixel order was last tuned at (tune_pixel_order)
 	bool poisoned = false; // a device-side error was reported: further render calls are refused
@@ -332,6 +337,8 @@ int apply_tiles(prgpu_scene* s, const prgpu_tile* tiles, uint32_t n_tiles)
 		if (tiles[i].x1 > s->cfg.width || tiles[i].y1 > s->cfg.height || tiles[i].x0 > tiles[i].x1 || tiles[i].y0 > tiles[i].y1)
 			return fail(PRGPU_EINVAL, "tile outside the film");
 	std::vector<uint32_t> pixels;
+	if (tiles != s->tiles.data())
+		s->tiles.assign(tiles, tiles + n_tiles);
 	prgpu_host::owned_pixels_morton(s->cfg.width, s->cfg.height, tiles, n_tiles, pixels);
 	s->n_slots = (uint32_t)pixels.size();
 	// Persistent mode with every owned pixel in flight at once (a small tile share: pixels <= path slots): no slot ever takes a
@@ -884,6 +891,56 @@ int render_iteration(prgpu_scene* s, uint32_t iter)
 	return PRGPU_OK;
 }
 
+// ---- ambient occlusion ------------------------------------------------------------------------------------------
+// One iteration of the AO pipeline (device/ao.inl) on the scene stream: camera rays and their closest hits as the lockstep pipeline's
+// first vertex, then hit records -> occlusion rays -> weights, then the filter taps and the running mean.  No host read-back: the
+// number of hits stays on the device (the counter the closest-hit launch zeroes), the occlusion grid is sized for every pixel hitting.
+int render_ao_iteration(prgpu_scene* s, uint32_t iter)
+{
+	if (!s->n_slots)
+		return PRGPU_OK;
+	hipStream_t st		   = s->stream;
+	prgpu_scene::Group& g0 = s->groups[0]; // (its closest-hit workspace and counters: the pixel groups are a `direct` pipeline matter)
+	const bool instr	   = s->instrument;
+	if (instr) {
+		const size_t np = s->n_pixels, n = np * s->ao.sample_count;
+		if (!s->ao.dbg_state) {
+			int rc = s->alloc(s->ao.dbg_state, np);
+			rc	   = rc == PRGPU_OK ? s->alloc(s->ao.dbg_org, 3 * n) : rc;
+			rc	   = rc == PRGPU_OK ? s->alloc(s->ao.dbg_dir, 3 * n) : rc;
+			rc	   = rc == PRGPU_OK ? s->alloc(s->ao.dbg_occluded, n) : rc;
+			if (rc != PRGPU_OK) {
+				s->ao.dbg_state = nullptr;
+				return rc;
+			}
+		}
+		HIP_TRY(hipMemsetAsync(s->ao.dbg_state, 0, np * 8, st));
+		HIP_TRY(hipMemsetAsync(s->ao.dbg_org, 0, n * 12, st));
+		HIP_TRY(hipMemsetAsync(s->ao.dbg_dir, 0, n * 12, st));
+		HIP_TRY(hipMemsetAsync(s->ao.dbg_occluded, 0, n, st));
+	}
+	s->time_begin(0, st);
+	prd::launch_raygen(s->sc, s->ps, 0, s->n_slots, iter, s->gstats, st);
+	s->time_end(st);
+	s->time_begin(1, st);
+	prd::launch_trace_closest(s->sc, s->ps, nullptr, 0, s->n_slots, instr, g0.ws_closest, g0.counters, s->gstats, st);
+	s->time_end(st);
+	s->time_begin(2, st);
+	prd::launch_ao_hits(s->sc, s->ps, s->ao, s->n_slots, instr, g0.counters, g0.ws_closest.queue_head, s->ws_ao.queue_head, s->gstats, st);
+	s->time_end(st);
+	s->time_begin(8, st);
+	prd::launch_ao_occlusion(s->sc, s->ps, s->ao, s->n_slots, instr, g0.counters, s->ws_ao, s->gstats, st);
+	s->time_end(st);
+	s->time_begin(2, st);
+	prd::launch_ao_splat(s->sc, s->ps, s->ao, s->n_slots, g0.counters, st);
+	s->time_end(st);
+	s->time_begin(4, st);
+	prd::launch_resolve(s->sc, s->ps, iter, st);
+	s->time_end(st);
+	HIP_TRY(hipGetLastError());
+	return PRGPU_OK;
+}
+
 // ---- streaming mode ---------------------------------------------------------------------------------------------
 // Pixels advance through their samples independently: when a path ends, its pixel's sum is folded into the running
 // mean and the pixel's next camera path joins the wavefront in the following round (k_regen).  The wavefront therefore
@@ -1376,6 +1433,15 @@ int prgpu_render(prgpu_scene* s, uint32_t iter_begin, uint32_t iter_end)
 	if (iter_end == iter_begin)
 		return PRGPU_OK;
 	s->reduced.valid = false; // the reduced frame is stale from here on: downloads read the rank's own planes until the next reduce
+	if (s->ao_enabled) {
+		for (uint32_t it = iter_begin; it < iter_end; ++it) {
+			const int rc = render_ao_iteration(s, it);
+			if (rc != PRGPU_OK)
+				return rc;
+			s->next_iteration = it + 1;
+		}
+		return PRGPU_OK;
+	}
 	if (s->mode != prgpu_scene::LOCKSTEP) {
 		const int rc = s->mode == prgpu_scene::PERSISTENT ? render_persistent(s, iter_begin, iter_end) : render_streaming(s, iter_begin, iter_end);
 		if (rc != PRGPU_OK)
@@ -1467,7 +1533,7 @@ int prgpu_trace_counters_get(prgpu_scene* s, prgpu_trace_counters* out)
 	HIP_TRY(hipMemcpy(host, s->gstats, sizeof(host), hipMemcpyDeviceToHost));
 	out->rays_closest  = s->rays_closest;
 	out->rays_any	   = s->rays_any;
-	if (s->mode == prgpu_scene::PERSISTENT) { // no per-launch host counts: every path ray is in the device statistics
+	if (s->mode == prgpu_scene::PERSISTENT || s->ao_enabled) { // no per-launch host counts: every path ray is in the device statistics
 		out->rays_closest += host[PRGPU_STAT_PRIMARY_RAYS] + host[PRGPU_STAT_BOUNCE_RAYS];
 		out->rays_any += host[PRGPU_STAT_SHADOW_RAYS];
 	}
@@ -2026,6 +2092,8 @@ int prgpu_enable_lpe(prgpu_scene* s, uint32_t n, const char* const* expressions)
 		return fail(PRGPU_EINVAL, "light path expressions are already enabled");
 	if (!n)
 		return PRGPU_OK;
+	if (s->ao_enabled) // (its one path, C<RD>E of LightPath::createCDL(1), is not built: refused, never a silently empty plane)
+		return fail(PRGPU_EUNSUPPORTED, "light path expressions are not provided with the ambient occlusion integrator");
 	HIP_TRY(hipSetDevice(s->device));
 	prd::DevLpe host;
 	std::memset(&host, 0, sizeof(host));
@@ -2075,6 +2143,81 @@ int prgpu_download_lpe(prgpu_scene* s, uint32_t index, float* xyz)
 	HIP_TRY(hipSetDevice(s->device));
 	HIP_TRY(hipStreamSynchronize(s->stream));
 	HIP_TRY(hipMemcpy(xyz, s->reduced.valid && index < s->reduced.lpe.size() ? s->reduced.lpe[index] : s->lpe_host.out[index], size_t(s->n_pixels) * 12, hipMemcpyDeviceToHost));
+	return PRGPU_OK;
+}
+
+int prgpu_enable_ambient_occlusion(prgpu_scene* s, uint32_t sample_count)
+{
+	if (!s)
+		return fail(PRGPU_EINVAL, "null scene");
+	if (s->next_iteration != 0)
+		return fail(PRGPU_EINVAL, "ambient occlusion must be enabled before the first iteration");
+	if (sample_count == 0)
+		return fail(PRGPU_EINVAL, "ambient occlusion needs a sample_count of at least 1");
+	if (uint64_t(s->n_pixels) * sample_count >= (1ull << 32))
+		return fail(PRGPU_EINVAL, "ambient occlusion: width * height * sample_count must stay below 2^32 (rays of one iteration)");
+	if (s->ps.lpe)
+		return fail(PRGPU_EUNSUPPORTED, "light path expressions are not provided with the ambient occlusion integrator");
+	if (s->ao_enabled)
+		return fail(PRGPU_EINVAL, "ambient occlusion is already enabled");
+	HIP_TRY(hipSetDevice(s->device));
+	prd::AoState ao{};
+	ao.sample_count = sample_count;
+	std::vector<uint64_t> jump(sample_count); // PCG_MULT^(2 k): sample k of a hit starts 2 k draws into the hit's stream
+	uint64_t acc = 1;
+	for (uint32_t k = 0; k < sample_count; ++k, acc *= prd::PCG_MULT * prd::PCG_MULT)
+		jump[k] = acc;
+	ao.jump_all = acc;
+	int rc = s->alloc(ao.rec, size_t(4) * s->n_pixels);
+	rc	   = rc == PRGPU_OK ? s->alloc(ao.occluded, s->n_pixels) : rc;
+	rc	   = rc == PRGPU_OK ? s->alloc(ao.counts, s->n_pixels, true) : rc;
+	rc	   = rc == PRGPU_OK ? s->upload(ao.jump, jump) : rc;
+	if (rc == PRGPU_OK && !s->ws_ao.queue_head) { // the ray service's grid: three blocks per CU (create_impl)
+		s->ws_ao = s->ws;
+		rc		 = s->alloc(s->ws_ao.queue_head, 1, true);
+		rc		 = rc == PRGPU_OK ? s->alloc(s->ws_ao.spill, prd::trace_workspace_spill_entries(s->ws_ao.max_blocks)) : rc;
+	}
+	if (rc != PRGPU_OK)
+		return rc;
+	HIP_TRY(hipStreamSynchronize(s->stream)); // (the table's host copy goes out of scope)
+	s->ao		  = ao;
+	s->ao_enabled = true;
+	s->mode		  = prgpu_scene::LOCKSTEP; // iteration-synchronous, every pixel filter; the owned pixels go back to plain Morton order
+	const std::vector<prgpu_tile> tiles = s->tiles;
+	return apply_tiles(s, tiles.data(), (uint32_t)tiles.size());
+}
+
+int prgpu_download_ao_counts(prgpu_scene* s, uint32_t* occluded)
+{
+	if (!s || !occluded)
+		return fail(PRGPU_EINVAL, "null argument");
+	if (!s->ao_enabled)
+		return fail(PRGPU_EINVAL, "ambient occlusion not enabled");
+	HIP_TRY(hipSetDevice(s->device));
+	HIP_TRY(hipStreamSynchronize(s->stream));
+	HIP_TRY(hipMemcpy(occluded, s->ao.counts, size_t(s->n_pixels) * 4, hipMemcpyDeviceToHost));
+	return PRGPU_OK;
+}
+
+int prgpu_download_ao_samples(prgpu_scene* s, uint64_t* rng_state, float* org, float* dir, uint8_t* occluded)
+{
+	if (!s)
+		return fail(PRGPU_EINVAL, "null scene");
+	if (!s->ao_enabled)
+		return fail(PRGPU_EINVAL, "ambient occlusion not enabled");
+	if (!s->instrument || !s->ao.dbg_state)
+		return fail(PRGPU_EINVAL, "the ambient occlusion ray record is kept only for iterations rendered with prgpu_set_instrumentation(s, 1)");
+	HIP_TRY(hipSetDevice(s->device));
+	HIP_TRY(hipStreamSynchronize(s->stream));
+	const size_t np = s->n_pixels, n = np * s->ao.sample_count;
+	if (rng_state)
+		HIP_TRY(hipMemcpy(rng_state, s->ao.dbg_state, np * 8, hipMemcpyDeviceToHost));
+	if (org)
+		HIP_TRY(hipMemcpy(org, s->ao.dbg_org, n * 12, hipMemcpyDeviceToHost));
+	if (dir)
+		HIP_TRY(hipMemcpy(dir, s->ao.dbg_dir, n * 12, hipMemcpyDeviceToHost));
+	if (occluded)
+		HIP_TRY(hipMemcpy(occluded, s->ao.dbg_occluded, n, hipMemcpyDeviceToHost));
 	return PRGPU_OK;
 }
 

@@ -41,7 +41,13 @@ class SceneBuilder:
         self._n_vertices = 0
         self._any_normals = False
         self._uv, self._any_uvs = [], False
+        self.integrator, self.ao_sample_count = abi.INTEGRATOR_DIRECT, 0
         self.set_camera(IDENTITY)
+
+    def ambient_occlusion(self, sample_count=10):
+        """(integrator :type 'ao' :sample_count N), ambientocclusion.cpp:107: a RenderContext of the built scene renders with it"""
+        assert int(sample_count) >= 1, "sample_count must be at least 1"
+        self.integrator, self.ao_sample_count = abi.INTEGRATOR_AO, int(sample_count)
 
     # ---- spectral nodes -------------------------------------------------------------------------
     def _add_spec(self, **kw):
@@ -423,6 +429,7 @@ class SceneData:
         d.n_lights = len(b.lights)
         d.lights = self.lights
         self.desc = d
+        self.integrator, self.ao_sample_count = b.integrator, b.ao_sample_count
 
     @property
     def settings(self):
@@ -466,6 +473,9 @@ class PrcScene:
         self._lib, self._h = lib, h
         self.desc = lib.prgpu_prc_desc(h).contents
         self.warnings = [w for w in lib.prgpu_prc_warnings(h).decode().split("\n") if w]
+        kind, count = C.c_uint32(), C.c_uint32()
+        abi.check(lib.prgpu_prc_integrator(h, C.byref(kind), C.byref(count)))
+        self.integrator, self.ao_sample_count = kind.value, count.value   # INTEGRATOR_DIRECT / INTEGRATOR_AO (:sample_count)
 
     def sky_params(self):
         """{light index: (sun elevation, sun azimuth, turbidity, albedo[11])} of the scene's sky lights (what their SkyModel was built from)."""
