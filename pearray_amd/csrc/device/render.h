@@ -61,9 +61,79 @@ struct PersistentTuning {
 void launch_path_persistent(const DevScene& sc, const PathState& ps, const uint32_t* owned, uint32_t n_owned, uint32_t iter_begin, uint32_t iter_end,
 							bool count, const TraceWorkspace& ws, const PersistentTuning& tune, int shader_waves /* of a block's four: 0 .. 2 */, uint32_t* next_pixel, uint32_t* error,
 							unsigned long long* gstats, hipStream_t st);
+// The compiled variants of the path kernel (either organisation), in order of preference: a scene runs the FIRST row whose mask covers its
+// features -- lean (Lambert / mesh / area lights), + smooth delta materials, everything but the rough / principled closures, everything but
+// light path expressions, everything.  The out-of-line closures are what the fourth row pays for: a kernel that CONTAINS the calls runs a
+// scene that never makes them 25 % slower (metal Cornell box: 3.18 vs 4.02 ms per iteration; leaving out spheres, AOVs + textures or
+// infinite / shape lights + planes instead changes nothing).  A variant for delta + rough materials only was measured and dropped: the
+// closures dominate such scenes, 156 vs 154 Msamples/s.  Light path expressions are a row of their own because their state tracking costs
+// the all-features kernel 7 % (C5 135 -> 125 Msamples/s); quadric entities ride in that top row.
+// A translation unit of render.hip takes its row by -DPR_VARIANT=<id>.  Adding a variant takes exactly two edits: a row here, and its id in
+// the Makefile's VARIANTS list.
+struct PathVariant {
+	int id;			   // PR_VARIANT of its translation units; bit id - 1 of PR_PL_VARIANTS
+	uint32_t features; // FEAT_* bits the kernel is compiled with
+};
+constexpr uint32_t FEAT_NO_LPE = FEAT_ALL & ~(FEAT_LPE | FEAT_QUADRICS), FEAT_NO_ROUGH = FEAT_NO_LPE & ~FEAT_ROUGH_MATERIALS;
+constexpr PathVariant PATH_VARIANTS[] = { { 1, 0u }, { 2, FEAT_DELTA_MATERIALS }, { 3, FEAT_NO_ROUGH }, { 4, FEAT_NO_LPE }, { 5, FEAT_ALL } };
+constexpr int N_PATH_VARIANTS		  = int(sizeof(PATH_VARIANTS) / sizeof(PATH_VARIANTS[0]));
+// index of the scene's row
+constexpr int path_variant(uint32_t features)
+{
+	for (int i = 0; i < N_PATH_VARIANTS - 1; ++i)
+		if ((features & ~PATH_VARIANTS[i].features) == 0u)
+			return i;
+	return N_PATH_VARIANTS - 1;
+}
+// index of the row with this id (N_PATH_VARIANTS: none)
+constexpr int path_variant_row(int id)
+{
+	int i = 0;
+	while (i < N_PATH_VARIANTS && PATH_VARIANTS[i].id != id)
+		++i;
+	return i;
+}
+constexpr bool path_variants_nested()
+{
+	for (int i = 0; i + 1 < N_PATH_VARIANTS; ++i)
+		if ((PATH_VARIANTS[i].features & ~PATH_VARIANTS[i + 1].features) != 0u)
+			return false;
+	return true;
+}
+static_assert(PATH_VARIANTS[N_PATH_VARIANTS - 1].features == FEAT_ALL, "the last variant must cover every scene");
+static_assert(path_variants_nested(), "each variant's mask must be contained in the next one's: then the first covering row is the smallest covering one");
+// The throughput organisation compiles every variant in these forms (its sub-units, -DPR_SUB=<index>): for 3 waves per SIMD with four-
+// or six-wide inner records, or for 2 waves per SIMD (one kernel for both widths), each plain and instrumented (COUNT).
+struct PathSub {
+	int occupancy;
+	bool wide, count;
+};
+constexpr PathSub PATH_SUBS[] = { { 3, false, false }, { 3, false, true }, { 2, false, false }, { 2, false, true }, { 3, true, false }, { 3, true, true } };
+constexpr int N_PATH_SUBS	  = int(sizeof(PATH_SUBS) / sizeof(PATH_SUBS[0]));
+// index of the sub-unit that serves a launch (N_PATH_SUBS: none)
+constexpr int path_sub(int occupancy, bool wide, bool count)
+{
+	const int occ = occupancy >= 3 ? 3 : 2;
+	int i		  = 0;
+	while (i < N_PATH_SUBS && !(PATH_SUBS[i].occupancy == occ && PATH_SUBS[i].count == count && (occ == 2 || PATH_SUBS[i].wide == wide)))
+		++i;
+	return i;
+}
+constexpr bool path_subs_complete()
+{
+	for (int k = 0; k < 8; ++k) // every (occupancy, wide, count) has a sub-unit ...
+		if (path_sub(2 + (k >> 2), (k & 2) != 0, (k & 1) != 0) >= N_PATH_SUBS)
+			return false;
+	for (int i = 0; i < N_PATH_SUBS; ++i) // ... and every sub-unit is the one its own row selects
+		if (path_sub(PATH_SUBS[i].occupancy, PATH_SUBS[i].wide, PATH_SUBS[i].count) != i)
+			return false;
+	return true;
+}
+static_assert(path_subs_complete(), "PATH_SUBS and path_sub disagree");
 // The latency organisation of the same kernel (device/path_wave.inl): a WAVE owns 64 .. 256 path slots with wave-private queues, two blocks
 // per CU at two waves per SIMD -- for tile shares whose pixel count is about the chip's lane count, where a launch lasts as long as its
-// deepest pixel's chain of vertices.  Same frame, bit for bit.
+// deepest pixel's chain of vertices.  Same frame, bit for bit.  Measured slower there than the throughput organisation,
+// so nothing selects it by default: PRGPU_PP_KERNEL=auto always runs the throughput kernel, and only PRGPU_PP_KERNEL=latency runs this one.
 struct LatencyGeometry {
 	uint32_t n_blocks, slots_per_wave, total_slots;
 };

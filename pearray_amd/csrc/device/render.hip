@@ -8,16 +8,23 @@
 //
 // No MFMA: no stage is a dense contraction.  The kernels are latency/bandwidth bound on BVH-node and
 // triangle fetches (64-byte inner and 128-byte leaf records, see DESIGN.md for the bytes-per-ray model).
-// This file is compiled thirty-five times (Makefile: -DPR_TU=0..5, 11..15, -DPR_SUB=0..5) so that the large kernels build in parallel: translation
-// unit 0 holds the wavefront (lockstep / streaming) kernels, the ray service and the launchers; units (v, s) hold ONE instantiation of the
-// persistent path kernel each (launch_pp_<v>_<s>).  The device functions above the kernels are shared source, not shared objects.
-#ifndef PR_TU
-#error "compile with -DPR_TU=0..5 or 11..15 (see the Makefile)"
+// This file is compiled once per translation unit (Makefile), so that the large kernels build in parallel: -DPR_UNIT=PR_WAVEFRONT is the
+// one unit that holds the wavefront (lockstep / streaming) kernels, the ray service and the host side of every launcher;
+// -DPR_UNIT=PR_THROUGHPUT -DPR_VARIANT=<id> -DPR_SUB=<index> holds ONE instantiation of the persistent path kernel (launch_pp<id, index>: a row
+// of PATH_VARIANTS x a row of PATH_SUBS, render.h) and -DPR_UNIT=PR_LATENCY -DPR_VARIANT=<id> -DPR_SUB=0|1 one of its latency organisation
+// (launch_pl<id, 0|1>: plain, instrumented).  The device functions above the kernels are shared source, not shared objects.
+#define PR_WAVEFRONT 1
+#define PR_THROUGHPUT 2
+#define PR_LATENCY 3
+#if !defined(PR_UNIT) || (PR_UNIT != PR_WAVEFRONT && PR_UNIT != PR_THROUGHPUT && PR_UNIT != PR_LATENCY)
+#error "compile with -DPR_UNIT=PR_WAVEFRONT, PR_THROUGHPUT or PR_LATENCY (see the Makefile)"
 #endif
 #include "render.h"
 
 #include <algorithm>
-#if PR_TU == 0
+#include <array>
+#include <utility>
+#if PR_UNIT == PR_WAVEFRONT
 #include <hipcub/hipcub.hpp>
 #endif
 
@@ -58,7 +65,7 @@ enum { CNT_NODES_CLOSEST = PRGPU_STAT_COUNT, CNT_TRIS_CLOSEST, CNT_NODES_ANY, CN
 #define PR_PP_BLOCK 256 // threads of a persistent-kernel block: 256 (three blocks per CU) or 768 (one block per CU: its twelve waves share one set of queues)
 #endif
 constexpr int PP_BLOCK		= PR_PP_BLOCK;
-constexpr int TRAV_BLOCK	= PR_TU >= 1 ? PP_BLOCK : 256; // the persistent-kernel units hold nothing but that kernel
+constexpr int TRAV_BLOCK	= PR_UNIT != PR_WAVEFRONT ? PP_BLOCK : 256; // the persistent-kernel units hold nothing but that kernel
 constexpr int STACK_LDS		= 16;
 constexpr int STACK_SPILL	= 64;  // additional entries per thread in global memory
 
@@ -210,18 +217,15 @@ __device__ __forceinline__ void inner_keys(const Trav& s, const float4& q0, cons
 }
 // ... sort part: continue with the nearest hit child and push the others far to near (occlusion rays share the sorted code: their
 // result does not depend on the order).  5-comparator network on the integer keys (misses sort last).
-template <int M, typename STK>
-__device__ __forceinline__ void trav_inner_rec(Trav& s, STK& st, const float4& q0, const float4& q1, const float4& q2, const float4& q3, bool wide, const uint2* top = nullptr)
+template <typename STK>
+__device__ __forceinline__ void sort_push_children(Trav& s, STK& st, uint32_t key[6], uint32_t base, bool wide)
 {
-	uint32_t key[6];
-	inner_keys(s, q0, q1, q2, q3, wide, key);
 #define PR_CSWAP(a, b)                                  \
 	{                                                   \
 		const uint32_t lo = min(key[a], key[b]);        \
 		key[b]			  = max(key[a], key[b]);        \
 		key[a]			  = lo;                         \
 	}
-	const uint32_t base = __float_as_uint(q2.z);
 	if (wide) { // 12-comparator network for six keys, then the two farthest
 		PR_CSWAP(0, 5) PR_CSWAP(1, 3) PR_CSWAP(2, 4) PR_CSWAP(1, 2) PR_CSWAP(3, 4) PR_CSWAP(0, 3) PR_CSWAP(2, 5) PR_CSWAP(0, 1) PR_CSWAP(2, 3) PR_CSWAP(4, 5) PR_CSWAP(1, 2) PR_CSWAP(3, 4)
 		st.reserve(5);
@@ -236,6 +240,13 @@ __device__ __forceinline__ void trav_inner_rec(Trav& s, STK& st, const float4& q
 	st.push_if(key[2] != 0xFFFFFFFFu, base + (key[2] & 0xFFu), key[2]);
 	st.push_if(key[1] != 0xFFFFFFFFu, base + (key[1] & 0xFFu), key[1]);
 	s.cur = key[0] != 0xFFFFFFFFu ? base + (key[0] & 0xFFu) : REC_EMPTY;
+}
+template <int M, typename STK>
+__device__ __forceinline__ void trav_inner_rec(Trav& s, STK& st, const float4& q0, const float4& q1, const float4& q2, const float4& q3, bool wide, const uint2* top = nullptr)
+{
+	uint32_t key[6];
+	inner_keys(s, q0, q1, q2, q3, wide, key);
+	sort_push_children(s, st, key, __float_as_uint(q2.z), wide);
 	trav_pop<M>(s, st, top);
 }
 template <int M>
@@ -973,7 +984,7 @@ __device__ __forceinline__ bool camera_path(const DevScene& sc, const PathState&
 	return has_ray;
 }
 
-#if PR_TU == 0
+#if PR_UNIT == PR_WAVEFRONT
 __global__ void __launch_bounds__(256) k_raygen(DevScene sc, PathState ps, uint32_t slot_base, uint32_t n_slots, uint32_t iter, unsigned long long* gstats)
 {
 	__shared__ BlockStats bs;
@@ -1041,7 +1052,7 @@ __global__ void __launch_bounds__(TRAV_BLOCK) k_trace_closest(DevScene sc, PathS
 	trace_persistent<false, COUNT>(sc, n_active, queue_head, spill, refill_below, load, store, gstats);
 }
 
-#endif // PR_TU == 0
+#endif // PR_UNIT == PR_WAVEFRONT
 // handleCameraVertex / handleDirectHit / handleNEE / handleScattering (direct.cpp:73-412), Walker::traverse
 // (vcm/Walker.h:23-54), handleZero (:459-464), IntegratorUtils::handleBackgroundGroup (IntegratorUtils.h:16-53).
 // Processes the path vertex of `slot` whose closest hit is in ps.st[slot].hit: adds emission, prepares the NEE shadow ray
@@ -2103,7 +2114,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 	}
 }
 
-#if PR_TU == 0
+#if PR_UNIT == PR_WAVEFRONT
 __global__ void __launch_bounds__(256) k_shade(DevScene sc, PathState ps, const uint32_t* __restrict__ active, uint32_t slot_base, uint32_t n_active,
 											  uint32_t* __restrict__ next_active, uint32_t* __restrict__ counters /* [0]=next, [1]=shadow, [2]=dead */,
 											  uint32_t* __restrict__ dead_list, uint32_t* queue_head_closest, uint32_t* queue_head_shadow,
@@ -2218,7 +2229,7 @@ __global__ void __launch_bounds__(256) k_resolve(DevScene sc, PathState ps, uint
 // clears the per-iteration plane of the pixels a path wrote (owned pixels are re-zeroed by raygen; this
 // covers nothing else, the plane is zero-initialised once) -- kept for symmetry with mCopySpectral->clear.
 
-#endif // PR_TU == 0
+#endif // PR_UNIT == PR_WAVEFRONT
 // ---- persistent path kernel -----------------------------------------------------------------------------------
 // The whole render call as ONE launch (single-tap pixel filters).  Every block owns `slots_per_block` path slots and two
 // ring queues in LDS -- rays to trace (closest and occlusion rays mixed) and vertices to shade -- and its four waves
@@ -2936,7 +2947,7 @@ __global__ void __launch_bounds__(TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu
 
 #include "path_wave.inl"
 
-#if PR_TU == 0
+#if PR_UNIT == PR_WAVEFRONT
 #include "ao.inl"
 
 // ---- ray service kernels (IArchive surface) ------------------------------------------------------------
@@ -2976,7 +2987,7 @@ struct SplitRing {
 };
 // ---- split traversal: leaf tests handed to whole waves through an LDS task queue (ray service, k_service_closest_split: one block-wide queue) ----
 // inner step of the split traversal: hit children that are leaves become tasks at once (they never enter the stack), the inner ones
-// are sorted and pushed as in trav_inner_rec.  Returns nothing; *n_tasks = leaves queued by this lane.
+// are sorted and pushed as in trav_inner_rec (sort_push_children).  Returns nothing; *n_tasks = leaves queued by this lane.
 template <bool WIDE, typename STK>
 __device__ __forceinline__ void trav_inner_split(Trav& s, STK& st, const float4& q0, const float4& q1, const float4& q2, const float4& q3, uint32_t* q, uint32_t* q_tail,
 												 uint32_t* pending_own, uint32_t tid, bool active, const uint32_t* q_head, uint32_t* overflow)
@@ -3021,26 +3032,7 @@ __device__ __forceinline__ void trav_inner_split(Trav& s, STK& st, const float4&
 #pragma unroll
 	for (int k = 0; k < NW; ++k)
 		key[k] = lf[k] ? 0xFFFFFFFFu : key[k];
-#define PR_CSWAP(a, b)                                  \
-	{                                                   \
-		const uint32_t lo = min(key[a], key[b]);        \
-		key[b]			  = max(key[a], key[b]);        \
-		key[a]			  = lo;                         \
-	}
-	if (WIDE) {
-		PR_CSWAP(0, 5) PR_CSWAP(1, 3) PR_CSWAP(2, 4) PR_CSWAP(1, 2) PR_CSWAP(3, 4) PR_CSWAP(0, 3) PR_CSWAP(2, 5) PR_CSWAP(0, 1) PR_CSWAP(2, 3) PR_CSWAP(4, 5) PR_CSWAP(1, 2) PR_CSWAP(3, 4)
-		st.reserve(5);
-		st.push_if(key[5] != 0xFFFFFFFFu, base + (key[5] & 0xFFu), key[5]);
-		st.push_if(key[4] != 0xFFFFFFFFu, base + (key[4] & 0xFFu), key[4]);
-	} else {
-		PR_CSWAP(0, 1) PR_CSWAP(2, 3) PR_CSWAP(0, 2) PR_CSWAP(1, 3) PR_CSWAP(1, 2)
-		st.reserve(3);
-	}
-#undef PR_CSWAP
-	st.push_if(key[3] != 0xFFFFFFFFu, base + (key[3] & 0xFFu), key[3]);
-	st.push_if(key[2] != 0xFFFFFFFFu, base + (key[2] & 0xFFu), key[2]);
-	st.push_if(key[1] != 0xFFFFFFFFu, base + (key[1] & 0xFFu), key[1]);
-	s.cur = key[0] != 0xFFFFFFFFu ? base + (key[0] & 0xFFu) : REC_EMPTY;
+	sort_push_children(s, st, key, base, WIDE);
 	trav_pop<MODE_CLOSEST>(s, st);
 }
 
@@ -3392,76 +3384,43 @@ void launch_ao_splat(const DevScene& sc, const PathState& ps, const AoState& ao,
 }
 bool ao_counts_folded() { return PR_AO_FOLD != 0; }
 
-#endif // PR_TU == 0
+#endif // PR_UNIT == PR_WAVEFRONT
 
-// ---- persistent path kernel: one translation unit per kernel (feature-mask variant x {3, 2 waves per SIMD} x {plain, instrumented}) ----
-[[maybe_unused]] constexpr uint32_t FEAT_NO_LPE = FEAT_ALL & ~(FEAT_LPE | FEAT_QUADRICS), FEAT_NO_ROUGH = FEAT_NO_LPE & ~FEAT_ROUGH_MATERIALS; // quadric entities ride in the top variant
-#define PR_PP_DECL(V, S) void launch_pp_##V##_##S(const DevScene& sc, const PathState& ps, const PersistentArgs& a, dim3 grid, hipStream_t st);
-#define PR_PP_DECL4(V) PR_PP_DECL(V, 0) PR_PP_DECL(V, 1) PR_PP_DECL(V, 2) PR_PP_DECL(V, 3) PR_PP_DECL(V, 4) PR_PP_DECL(V, 5)
-PR_PP_DECL4(1) PR_PP_DECL4(2) PR_PP_DECL4(3) PR_PP_DECL4(4) PR_PP_DECL4(5)
-#define PR_PL_DECL(V) void launch_pl_##V##_0(const DevScene& sc, const PathState& ps, const WaveArgs& a, dim3 grid, hipStream_t st); \
-	void launch_pl_##V##_1(const DevScene& sc, const PathState& ps, const WaveArgs& a, dim3 grid, hipStream_t st);
-PR_PL_DECL(1) PR_PL_DECL(2) PR_PL_DECL(3) PR_PL_DECL(4) PR_PL_DECL(5)
-#if PR_TU >= 1
-#ifndef PR_SUB
-#error "compile the persistent-kernel units with -DPR_SUB=0..5"
+// ---- persistent path kernel: one translation unit per kernel (PATH_VARIANTS x PATH_SUBS, and PATH_VARIANTS x {plain, instrumented} of the latency organisation) ----
+template <int VARIANT, int SUB>
+void launch_pp(const DevScene& sc, const PathState& ps, const PersistentArgs& a, dim3 grid, hipStream_t st);
+template <int VARIANT, int SUB>
+void launch_pl(const DevScene& sc, const PathState& ps, const WaveArgs& a, dim3 grid, hipStream_t st);
+#if PR_UNIT != PR_WAVEFRONT
+#if !defined(PR_VARIANT) || !defined(PR_SUB)
+#error "compile the persistent-kernel units with -DPR_VARIANT=<id of a row of PATH_VARIANTS> -DPR_SUB=<index>"
 #endif
-// units 11..15 hold the latency organisation of variants 1..5 (a literal: it is pasted into the launcher's name)
-#if PR_TU == 1 || PR_TU == 11
-#define PR_VARIANT 1
-#elif PR_TU == 2 || PR_TU == 12
-#define PR_VARIANT 2
-#elif PR_TU == 3 || PR_TU == 13
-#define PR_VARIANT 3
-#elif PR_TU == 4 || PR_TU == 14
-#define PR_VARIANT 4
-#else
-#define PR_VARIANT 5
-#endif
-#if PR_VARIANT == 1
-#define PR_PP_FEATS 0u
-#elif PR_VARIANT == 2
-#define PR_PP_FEATS FEAT_DELTA_MATERIALS
-#elif PR_VARIANT == 3
-#define PR_PP_FEATS FEAT_NO_ROUGH
-#elif PR_VARIANT == 4
-#define PR_PP_FEATS FEAT_NO_LPE
-#else
-#define PR_PP_FEATS FEAT_ALL // + light path expressions: their state tracking costs the all-features kernel 7 % (C5 135 -> 125 Msamples/s), so it is its own variant
-#endif
-#define PR_PP_CAT2(P, V, S) launch_##P##_##V##_##S
-#define PR_PP_CAT(P, V, S) PR_PP_CAT2(P, V, S)
-#if PR_TU > 10
-void PR_PP_CAT(pl, PR_VARIANT, PR_SUB)(const DevScene& sc, const PathState& ps, const WaveArgs& a, dim3 grid, hipStream_t st)
+static_assert(path_variant_row(PR_VARIANT) < N_PATH_VARIANTS, "PR_VARIANT is not the id of a row of PATH_VARIANTS");
+#if PR_UNIT == PR_LATENCY
+template <int VARIANT, int SUB>
+void launch_pl(const DevScene& sc, const PathState& ps, const WaveArgs& a, dim3 grid, hipStream_t st)
 {
-#if PR_SUB == 0
-	hipLaunchKernelGGL((k_path_latency<false, PR_PP_FEATS>), grid, dim3(TRAV_BLOCK), 0, st, sc, ps, a);
-#else
-	hipLaunchKernelGGL((k_path_latency<true, PR_PP_FEATS>), grid, dim3(TRAV_BLOCK), 0, st, sc, ps, a);
-#endif
+	static_assert(SUB == 0 || SUB == 1, "latency units: PR_SUB=0 (plain) or 1 (instrumented)");
+	hipLaunchKernelGGL((k_path_latency<SUB != 0, PATH_VARIANTS[path_variant_row(VARIANT)].features>), grid, dim3(TRAV_BLOCK), 0, st, sc, ps, a);
 }
+template void launch_pl<PR_VARIANT, PR_SUB>(const DevScene&, const PathState&, const WaveArgs&, dim3, hipStream_t);
 #else
-void PR_PP_CAT(pp, PR_VARIANT, PR_SUB)(const DevScene& sc, const PathState& ps, const PersistentArgs& a, dim3 grid, hipStream_t st)
+template <int VARIANT, int SUB>
+void launch_pp(const DevScene& sc, const PathState& ps, const PersistentArgs& a, dim3 grid, hipStream_t st)
 {
+	constexpr PathSub u		 = PATH_SUBS[SUB]; // (PR_SUB: an index into PATH_SUBS)
+	constexpr uint32_t FEATS = PATH_VARIANTS[path_variant_row(VARIANT)].features;
 	const dim3 block(TRAV_BLOCK);
-#if PR_SUB == 0
-	hipLaunchKernelGGL((k_path_persistent_occ3<false, PR_PP_FEATS, false>), grid, block, 0, st, sc, ps, a);
-#elif PR_SUB == 1
-	hipLaunchKernelGGL((k_path_persistent_occ3<true, PR_PP_FEATS, false>), grid, block, 0, st, sc, ps, a);
-#elif PR_SUB == 2
-	hipLaunchKernelGGL((k_path_persistent<false, PR_PP_FEATS>), grid, block, 0, st, sc, ps, a);
-#elif PR_SUB == 3
-	hipLaunchKernelGGL((k_path_persistent<true, PR_PP_FEATS>), grid, block, 0, st, sc, ps, a);
-#elif PR_SUB == 4 // the 3-waves-per-SIMD kernel for scenes whose inner records hold six children
-	hipLaunchKernelGGL((k_path_persistent_occ3<false, PR_PP_FEATS, true>), grid, block, 0, st, sc, ps, a);
-#else
-	hipLaunchKernelGGL((k_path_persistent_occ3<true, PR_PP_FEATS, true>), grid, block, 0, st, sc, ps, a);
-#endif
+	if constexpr (u.occupancy == 3)
+		hipLaunchKernelGGL((k_path_persistent_occ3<u.count, FEATS, u.wide>), grid, block, 0, st, sc, ps, a);
+	else
+		hipLaunchKernelGGL((k_path_persistent<u.count, FEATS>), grid, block, 0, st, sc, ps, a);
 }
+template void launch_pp<PR_VARIANT, PR_SUB>(const DevScene&, const PathState&, const PersistentArgs&, dim3, hipStream_t);
 #endif
-#endif // PR_TU >= 1
+#endif // PR_UNIT != PR_WAVEFRONT
 
-#if PR_TU == 0
+#if PR_UNIT == PR_WAVEFRONT
 PersistentGeometry persistent_geometry(uint32_t n_owned, uint32_t max_blocks, uint32_t max_slots_per_block)
 {
 	PersistentGeometry g;
@@ -3483,6 +3442,30 @@ uint32_t persistent_slot_padding() { return PP_SLOTS_MAX; }
 uint32_t slot_array_padding() { return std::max<uint32_t>(PP_SLOTS_MAX, (TRAV_BLOCK / 64u) * PW_SLOTS_MAX); } // (the latency grid rounds up to whole blocks of four waves)
 uint32_t persistent_block_threads() { return PP_BLOCK; }
 int shade_ticks_counter() { return CNT_SHADE_TICKS; } // ... followed by CNT_IDLE_TICKS, CNT_TOTAL_TICKS
+
+// The host's launcher tables, one row per row of PATH_VARIANTS (the launchers themselves are instantiated in their own units)
+typedef void (*PpLaunchFn)(const DevScene&, const PathState&, const PersistentArgs&, dim3, hipStream_t);
+typedef void (*PlLaunchFn)(const DevScene&, const PathState&, const WaveArgs&, dim3, hipStream_t);
+template <int... I> // entry variant row * N_PATH_SUBS + sub-unit
+constexpr std::array<PpLaunchFn, sizeof...(I)> pp_launch_table(std::integer_sequence<int, I...>)
+{
+	return { { launch_pp<PATH_VARIANTS[I / N_PATH_SUBS].id, I % N_PATH_SUBS>... } };
+}
+// PR_PL_VARIANTS (a development aid): bit id - 1 says that the library holds the latency organisation of variant id; the others get no entry
+constexpr bool pl_variant_built(int row) { return ((PR_PL_VARIANTS >> (PATH_VARIANTS[row].id - 1)) & 1u) != 0u; }
+template <int ROW, int SUB>
+constexpr PlLaunchFn pl_launcher()
+{
+	if constexpr (pl_variant_built(ROW))
+		return launch_pl<PATH_VARIANTS[ROW].id, SUB>;
+	else
+		return nullptr;
+}
+template <int... I> // entry variant row * 2 + (instrumented ? 1 : 0)
+constexpr std::array<PlLaunchFn, sizeof...(I)> pl_launch_table(std::integer_sequence<int, I...>)
+{
+	return { { pl_launcher<I / 2, I % 2>()... } };
+}
 
 void launch_path_persistent(const DevScene& sc, const PathState& ps, const uint32_t* owned, uint32_t n_owned, uint32_t iter_begin, uint32_t iter_end,
 							bool count, const TraceWorkspace& ws, const PersistentTuning& tune, int shader_waves, uint32_t* next_pixel, uint32_t* error,
@@ -3521,18 +3504,8 @@ void launch_path_persistent(const DevScene& sc, const PathState& ps, const uint3
 		a.bl_cap = 0;
 	(void)hipMemsetAsync(next_pixel, 0, sizeof(uint32_t), st);
 	const dim3 grid(g.n_blocks);
-	// smallest compiled variant that covers the scene's features: lean (Lambert / mesh / area lights), + smooth delta materials,
-	// everything but the rough / principled closures, everything.  The out-of-line closures are what the last step pays for: a kernel
-	// that CONTAINS the calls runs a scene that never makes them 25 % slower (metal Cornell box: 3.18 vs 4.02 ms per iteration; leaving
-	// out spheres, AOVs + textures or infinite / shape lights + planes instead changes nothing).  A variant for delta + rough materials
-	// only was measured and dropped: the closures dominate such scenes, 156 vs 154 Msamples/s.
-	typedef void (*LaunchFn)(const DevScene&, const PathState&, const PersistentArgs&, dim3, hipStream_t);
-#define PR_PP_ROW(V) { launch_pp_##V##_0, launch_pp_##V##_1, launch_pp_##V##_2, launch_pp_##V##_3, launch_pp_##V##_4, launch_pp_##V##_5 }
-	static const LaunchFn table[5][6] = { PR_PP_ROW(1), PR_PP_ROW(2), PR_PP_ROW(3), PR_PP_ROW(4), PR_PP_ROW(5) };
-#undef PR_PP_ROW
-	const int variant = (sc.features & (FEAT_LPE | FEAT_QUADRICS)) ? 4
-						: (sc.features == 0 ? 0 : ((sc.features & ~FEAT_DELTA_MATERIALS) == 0 ? 1 : ((sc.features & FEAT_ROUGH_MATERIALS) == 0 ? 2 : 3)));
-	table[variant][(tune.occupancy >= 3 ? (sc.bvh_wide ? 4 : 0) : 2) + (count ? 1 : 0)](sc, ps, a, grid, st);
+	static constexpr auto table = pp_launch_table(std::make_integer_sequence<int, N_PATH_VARIANTS * N_PATH_SUBS>{});
+	table[path_variant(sc.features) * N_PATH_SUBS + path_sub(tune.occupancy, sc.bvh_wide != 0u, count)](sc, ps, a, grid, st);
 }
 
 // The latency organisation (path_wave.inl): waves that own their paths.  Grid: as many waves as the pixels need at `slots_per_wave` slots
@@ -3556,8 +3529,7 @@ LatencyGeometry latency_geometry(uint32_t n_owned, uint32_t max_blocks_throughpu
 }
 bool latency_variant_built(uint32_t features)
 {
-	const int variant = (features & (FEAT_LPE | FEAT_QUADRICS)) ? 4 : (features == 0 ? 0 : ((features & ~FEAT_DELTA_MATERIALS) == 0 ? 1 : ((features & FEAT_ROUGH_MATERIALS) == 0 ? 2 : 3)));
-	return ((PR_PL_VARIANTS >> variant) & 1u) != 0u;
+	return pl_variant_built(path_variant(features));
 }
 void launch_path_latency(const DevScene& sc, const PathState& ps, const uint32_t* owned, uint32_t n_owned, uint32_t iter_begin, uint32_t iter_end, bool count,
 						 const TraceWorkspace& ws, const LatencyTuning& tune, uint32_t* error, unsigned long long* gstats, hipStream_t st)
@@ -3576,43 +3548,14 @@ void launch_path_latency(const DevScene& sc, const PathState& ps, const uint32_t
 	a.refill_below	 = std::min(64, std::max(1, tune.refill_below));
 	a.shade_min		 = (uint32_t)std::min(64, std::max(1, tune.shade_min));
 	a.gstats		 = gstats;
-	typedef void (*LaunchFn)(const DevScene&, const PathState&, const WaveArgs&, dim3, hipStream_t);
-	// (a variant the library was built without -- PR_PL_VARIANTS, a development aid -- has no entry: the host asks latency_variant_built first)
-	static const LaunchFn table[5][2] = {
-#if PR_PL_VARIANTS & 1
-		{ launch_pl_1_0, launch_pl_1_1 },
-#else
-		{ nullptr, nullptr },
-#endif
-#if PR_PL_VARIANTS & 2
-		{ launch_pl_2_0, launch_pl_2_1 },
-#else
-		{ nullptr, nullptr },
-#endif
-#if PR_PL_VARIANTS & 4
-		{ launch_pl_3_0, launch_pl_3_1 },
-#else
-		{ nullptr, nullptr },
-#endif
-#if PR_PL_VARIANTS & 8
-		{ launch_pl_4_0, launch_pl_4_1 },
-#else
-		{ nullptr, nullptr },
-#endif
-#if PR_PL_VARIANTS & 16
-		{ launch_pl_5_0, launch_pl_5_1 },
-#else
-		{ nullptr, nullptr },
-#endif
-	};
-	const int variant = (sc.features & (FEAT_LPE | FEAT_QUADRICS)) ? 4
-						: (sc.features == 0 ? 0 : ((sc.features & ~FEAT_DELTA_MATERIALS) == 0 ? 1 : ((sc.features & FEAT_ROUGH_MATERIALS) == 0 ? 2 : 3)));
-	if (LaunchFn fn = table[variant][count ? 1 : 0])
+	// (a variant the library was built without has no entry: the host asks latency_variant_built first)
+	static constexpr auto table = pl_launch_table(std::make_integer_sequence<int, N_PATH_VARIANTS * 2>{});
+	if (PlLaunchFn fn = table[path_variant(sc.features) * 2 + (count ? 1 : 0)])
 		fn(sc, ps, a, dim3(g.n_blocks), st);
 }
 
 uint32_t trace_stack_capacity() { return (uint32_t)(STACK_LDS + STACK_SPILL); }
 size_t trace_workspace_spill_entries(uint32_t max_blocks) { return size_t(max_blocks) * std::max(TRAV_BLOCK, PP_BLOCK) * STACK_SPILL; }
-#endif // PR_TU == 0
+#endif // PR_UNIT == PR_WAVEFRONT
 
 } // namespace prd

@@ -7,6 +7,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -45,13 +46,13 @@ namespace {
 // ---- environment knobs: every one the library reads, in one place ------------------------------------------------------------------
 // Development and test aids.  None of them changes a rendered value (tests/test_gpu_parity.py runs the scheduling ones against the
 // checker); the defaults are the measured optima quoted in DESIGN.md.  Scene-shaping knobs are read once, when a scene is created.
+constexpr int KNOB_INVALID = INT_MIN; // what an enumerated knob holds when its variable is set to a text it does not list (scene creation then fails)
 struct Knobs {
 	int mode = -1;						  // PRGPU_MODE=lockstep|streaming|persistent (0 / 1 / 2; -1: default = persistent)
-	bool mode_invalid = false;
 	prd::PersistentTuning pp;			  // PRGPU_PP_SLOTS, _SHADE_MIN, _SHADE_PARTIAL, _FIN_BATCH, _OCCUPANCY, _SHADER, _RESIDENT
 	bool pp_slots_set		   = false;
-	int pp_kernel			   = 0;		  // PRGPU_PP_KERNEL=throughput|latency (1 / 2; 0: by the size of the tile share, render_persistent)
-	bool pp_kernel_invalid	   = false;
+	int pp_kernel			   = 0;		  // PRGPU_PP_KERNEL=auto|throughput|latency (0 / 1 / 2).  auto ALWAYS runs the throughput kernel: the latency organisation
+										  // measured equal at best and up to 2.5 x slower on the small tile shares it was made for, so only `latency` selects it
 	prd::LatencyTuning pl;				  // PRGPU_PL_SLOTS, _SHADE_MIN, _REFILL: the latency organisation's slots per wave (cap), shading and refill thresholds
 	int pp_refill			   = 48;	  // PRGPU_PP_REFILL: a wave refills its idle lanes when fewer than this many hold a ray
 	int pp_blocks_per_cu	   = 0;		  // PRGPU_PP_BLOCKS_PER_CU (0: 768 threads per CU)
@@ -68,12 +69,10 @@ struct Knobs {
 	bool debug_counters		   = false;	  // PRGPU_DEBUG_COUNTERS: print the instrumented kernel's time split
 	const char* dump_block_life = nullptr; // PRGPU_DUMP_BLOCK_LIFE=<file>: per-block lifetimes of the last instrumented launch
 	int bvh_width			   = 0;		  // PRGPU_BVH_WIDTH=auto|4|6: children per inner BVH record (0 = auto: the tree whose estimated cost is lower, device/bvh.hip)
-	bool bvh_width_invalid	   = false;
 	int bvh_top				   = -1;	  // PRGPU_BVH_TOP=auto|file|area|morton: the order of the entities at the top of the tree (0 / 1 / 2; -1 = auto: all three are built, the cheapest
 										  // is kept).  A scene of one entity has no top to choose: prgpu_pipeline_info's bvh_top says what was built.
 	int bvh_parity			   = -1;	  // PRGPU_BVH_PARITY=auto|even|odd: which depths of the radix tree become four-wide records (0 / 1; -1 = auto: the cheaper one that fits the stack).
 										  // Test aids: the trees `auto` would not pick for a scene are walked on purpose (tests/test_gpu_bvh_width.py); no effect on a six-wide tree.
-	bool bvh_top_invalid = false, bvh_parity_invalid = false;
 	int trace_ranges		   = -1;	  // PRGPU_TRACE_RANGES=1: load the roctx library for the named ranges even when no profiler brought it along; 0: never emit ranges
 };
 Knobs read_knobs()
@@ -82,27 +81,22 @@ Knobs read_knobs()
 		const char* env = getenv(name);
 		return env ? std::min(hi, std::max(lo, atoll(env))) : def;
 	};
+	// an enumerated knob: the value listed for the variable's text, `def` when it is unset, KNOB_INVALID for any other text
+	auto choice = [](const char* name, std::initializer_list<std::pair<const char*, int>> choices, int def) -> int {
+		const char* env = getenv(name);
+		if (!env)
+			return def;
+		for (const auto& c : choices)
+			if (std::strcmp(env, c.first) == 0)
+				return c.second;
+		return KNOB_INVALID;
+	};
 	Knobs k;
-	if (const char* env = getenv("PRGPU_MODE")) {
-		k.mode		   = std::strcmp(env, "lockstep") == 0 ? 0 : (std::strcmp(env, "streaming") == 0 ? 1 : (std::strcmp(env, "persistent") == 0 ? 2 : -1));
-		k.mode_invalid = k.mode < 0;
-	}
-	if (const char* env = getenv("PRGPU_PP_KERNEL")) {
-		k.pp_kernel			= std::strcmp(env, "throughput") == 0 ? 1 : (std::strcmp(env, "latency") == 0 ? 2 : (std::strcmp(env, "auto") == 0 ? 0 : -1));
-		k.pp_kernel_invalid = k.pp_kernel < 0;
-	}
-	if (const char* env = getenv("PRGPU_BVH_WIDTH")) {
-		k.bvh_width			= std::strcmp(env, "auto") == 0 ? 0 : (std::strcmp(env, "4") == 0 ? 4 : (std::strcmp(env, "6") == 0 ? 6 : -1));
-		k.bvh_width_invalid = k.bvh_width < 0;
-	}
-	if (const char* env = getenv("PRGPU_BVH_TOP")) {
-		k.bvh_top		  = std::strcmp(env, "auto") == 0 ? -1 : (std::strcmp(env, "file") == 0 ? 0 : (std::strcmp(env, "area") == 0 ? 1 : (std::strcmp(env, "morton") == 0 ? 2 : -2)));
-		k.bvh_top_invalid = k.bvh_top < -1;
-	}
-	if (const char* env = getenv("PRGPU_BVH_PARITY")) {
-		k.bvh_parity		 = std::strcmp(env, "auto") == 0 ? -1 : (std::strcmp(env, "even") == 0 ? 0 : (std::strcmp(env, "odd") == 0 ? 1 : -2));
-		k.bvh_parity_invalid = k.bvh_parity < -1;
-	}
+	k.mode		 = choice("PRGPU_MODE", { { "lockstep", 0 }, { "streaming", 1 }, { "persistent", 2 } }, k.mode);
+	k.pp_kernel	 = choice("PRGPU_PP_KERNEL", { { "auto", 0 }, { "throughput", 1 }, { "latency", 2 } }, k.pp_kernel);
+	k.bvh_width	 = choice("PRGPU_BVH_WIDTH", { { "auto", 0 }, { "4", 4 }, { "6", 6 } }, k.bvh_width);
+	k.bvh_top	 = choice("PRGPU_BVH_TOP", { { "auto", -1 }, { "file", 0 }, { "area", 1 }, { "morton", 2 } }, k.bvh_top);
+	k.bvh_parity = choice("PRGPU_BVH_PARITY", { { "auto", -1 }, { "even", 0 }, { "odd", 1 } }, k.bvh_parity);
 	k.pl.slots_per_wave	  = (uint32_t)num("PRGPU_PL_SLOTS", k.pl.slots_per_wave, 64, 256);
 	k.pl.shade_min		  = (int)num("PRGPU_PL_SHADE_MIN", k.pl.shade_min, 1, 64);
 	k.pl.refill_below	  = (int)num("PRGPU_PL_REFILL", k.pl.refill_below, 1, 64);
@@ -180,8 +174,9 @@ struct TimedLaunch {
 	hipEvent_t start, stop;
 	int family;
 };
-const char* const FAMILY_NAMES[] = { "raygen", "trace_closest", "shade", "trace_any", "resolve", "sort", "path", "reduce", "ao" };
-constexpr int N_FAMILIES		 = 9;
+enum Family { FAM_RAYGEN, FAM_TRACE_CLOSEST, FAM_SHADE, FAM_TRACE_ANY, FAM_RESOLVE, FAM_SORT, FAM_PATH, FAM_REDUCE, FAM_AO, N_FAMILIES };
+const char* const FAMILY_NAMES[] = { "raygen", "trace_closest", "shade", "trace_any", "resolve", "sort", "path", "reduce", "ao" }; // in the order of Family
+static_assert(sizeof(FAMILY_NAMES) / sizeof(FAMILY_NAMES[0]) == N_FAMILIES, "one name per timing family");
 
 } // namespace
 
@@ -297,7 +292,7 @@ struct prgpu_scene {
 		return upload(ptr, v.data(), v.size());
 	}
 
-	void time_begin(int family, hipStream_t st)
+	void time_begin(Family family, hipStream_t st)
 	{
 		if (!timing)
 			return;
@@ -590,11 +585,11 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 
 	// device LBVH
 	prd::BvhBuildInput bin{ d->n_triangles, d->n_entities, sc.positions, sc.indices, sc.tri_entity, sc.entities, sc.tri_class };
-	if (s->knobs.bvh_width_invalid)
+	if (s->knobs.bvh_width == KNOB_INVALID)
 		return fail(PRGPU_EINVAL, "PRGPU_BVH_WIDTH must be auto, 4 or 6");
-	if (s->knobs.bvh_top_invalid)
+	if (s->knobs.bvh_top == KNOB_INVALID)
 		return fail(PRGPU_EINVAL, "PRGPU_BVH_TOP must be auto, file, area or morton");
-	if (s->knobs.bvh_parity_invalid)
+	if (s->knobs.bvh_parity == KNOB_INVALID)
 		return fail(PRGPU_EINVAL, "PRGPU_BVH_PARITY must be auto, even or odd");
 	bin.width = s->knobs.bvh_width;
 	bin.top	  = s->knobs.bvh_top;
@@ -672,9 +667,9 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 	// streaming (pixels advance through their samples independently) is bit-identical for single-tap filters but measured ~6 % slower than
 	// the iteration-synchronous pipeline on MI355X (finished paths wait one round before their pixel's next sample starts)
 	s->mode = prgpu_scene::PERSISTENT;
-	if (s->knobs.mode_invalid)
+	if (s->knobs.mode == KNOB_INVALID)
 		return fail(PRGPU_EINVAL, "PRGPU_MODE must be lockstep, streaming or persistent");
-	if (s->knobs.pp_kernel_invalid)
+	if (s->knobs.pp_kernel == KNOB_INVALID)
 		return fail(PRGPU_EINVAL, "PRGPU_PP_KERNEL must be auto, throughput or latency");
 	if (s->knobs.mode == 0)
 		s->mode = prgpu_scene::LOCKSTEP;
@@ -770,12 +765,12 @@ int enqueue_vertex(prgpu_scene* s, prgpu_scene::Group& g)
 				return rc;
 			g.sort_temp = tmp;
 		}
-		s->time_begin(5, st);
+		s->time_begin(FAM_SORT, st);
 		prd::launch_sort_active(s->sc, g.ps, g.active, g.n_active, g.sort_keys_a, g.sort_keys_b, g.sort_active, g.sort_temp, g.sort_temp_bytes, st);
 		s->time_end(st);
 		g.active = g.sort_active; // the shading pass reads the same list (g.next is written, never this one)
 	}
-	s->time_begin(1, st);
+	s->time_begin(FAM_TRACE_CLOSEST, st);
 	prd::launch_trace_closest(s->sc, g.ps, g.active, g.slot_begin, g.n_active, s->instrument, g.ws_closest, g.counters, s->gstats, st);
 	s->time_end(st);
 	s->rays_closest += g.n_active;
@@ -783,7 +778,7 @@ int enqueue_vertex(prgpu_scene* s, prgpu_scene::Group& g)
 		HIP_TRY(hipStreamWaitEvent(st, g.ev_shadow, 0));
 		g.shadow_pending = false;
 	}
-	s->time_begin(2, st);
+	s->time_begin(FAM_SHADE, st);
 	prd::launch_shade(s->sc, g.ps, g.active, g.slot_begin, g.n_active, g.next, g.counters, nullptr, g.ws_closest.queue_head, g.ws_shadow.queue_head,
 					  s->gstats, st);
 	s->time_end(st);
@@ -802,7 +797,7 @@ int render_iteration(prgpu_scene* s, uint32_t iter)
 			continue;
 		if (s->resolve_recorded && g.s_main != s->stream)
 			HIP_TRY(hipStreamWaitEvent(g.s_main, s->ev_resolve, 0)); // raygen clears what the last resolve read
-		s->time_begin(0, g.s_main);
+		s->time_begin(FAM_RAYGEN, g.s_main);
 		prd::launch_raygen(s->sc, g.ps, g.slot_begin, g.n_slots, iter, s->gstats, g.s_main);
 		s->time_end(g.s_main);
 		g.active		 = nullptr; // identity list for the primary wave
@@ -832,7 +827,7 @@ int render_iteration(prgpu_scene* s, uint32_t iter)
 			const uint32_t n_shadow = g.h_counters[1];
 			if (n_shadow) { // NEE visibility on the side stream, overlapping the next closest-hit launch
 				HIP_TRY(hipStreamWaitEvent(g.s_shadow, g.ev_shade, 0));
-				s->time_begin(3, g.s_shadow);
+				s->time_begin(FAM_TRACE_ANY, g.s_shadow);
 				prd::launch_trace_shadow(s->sc, g.ps, n_shadow, s->instrument, g.ws_shadow, s->gstats, g.s_shadow);
 				s->time_end(g.s_shadow);
 				HIP_TRY(hipEventRecord(g.ev_shadow, g.s_shadow));
@@ -871,7 +866,7 @@ int render_iteration(prgpu_scene* s, uint32_t iter)
 		if (g.s_main != s->stream)
 			HIP_TRY(hipStreamWaitEvent(s->stream, g.ev_shade, 0));
 	}
-	s->time_begin(4, s->stream);
+	s->time_begin(FAM_RESOLVE, s->stream);
 	prd::launch_resolve(s->sc, s->ps, iter, s->stream);
 	s->time_end(s->stream);
 	if (s->ps.lpe) { // the light path expressions' planes resolve like the main one (LocalFrameOutputDevice.cpp:99-113: same weights)
@@ -919,22 +914,22 @@ int render_ao_iteration(prgpu_scene* s, uint32_t iter)
 		HIP_TRY(hipMemsetAsync(s->ao.dbg_dir, 0, n * 12, st));
 		HIP_TRY(hipMemsetAsync(s->ao.dbg_occluded, 0, n, st));
 	}
-	s->time_begin(0, st);
+	s->time_begin(FAM_RAYGEN, st);
 	prd::launch_raygen(s->sc, s->ps, 0, s->n_slots, iter, s->gstats, st);
 	s->time_end(st);
-	s->time_begin(1, st);
+	s->time_begin(FAM_TRACE_CLOSEST, st);
 	prd::launch_trace_closest(s->sc, s->ps, nullptr, 0, s->n_slots, instr, g0.ws_closest, g0.counters, s->gstats, st);
 	s->time_end(st);
-	s->time_begin(2, st);
+	s->time_begin(FAM_SHADE, st);
 	prd::launch_ao_hits(s->sc, s->ps, s->ao, s->n_slots, instr, g0.counters, g0.ws_closest.queue_head, s->ws_ao.queue_head, s->gstats, st);
 	s->time_end(st);
-	s->time_begin(8, st);
+	s->time_begin(FAM_AO, st);
 	prd::launch_ao_occlusion(s->sc, s->ps, s->ao, s->n_slots, instr, g0.counters, s->ws_ao, s->gstats, st);
 	s->time_end(st);
-	s->time_begin(2, st);
+	s->time_begin(FAM_SHADE, st);
 	prd::launch_ao_splat(s->sc, s->ps, s->ao, s->n_slots, g0.counters, st);
 	s->time_end(st);
-	s->time_begin(4, st);
+	s->time_begin(FAM_RESOLVE, st);
 	prd::launch_resolve(s->sc, s->ps, iter, st);
 	s->time_end(st);
 	HIP_TRY(hipGetLastError());
@@ -951,7 +946,7 @@ int enqueue_round(prgpu_scene* s, prgpu_scene::Group& g, uint32_t iter_end)
 {
 	hipStream_t st = g.s_main;
 	if (g.n_active) {
-		s->time_begin(1, st);
+		s->time_begin(FAM_TRACE_CLOSEST, st);
 		prd::launch_trace_closest(s->sc, g.ps, g.active, g.slot_begin, g.n_active, s->instrument, g.ws_closest, g.counters, s->gstats, st);
 		s->time_end(st);
 		s->rays_closest += g.n_active;
@@ -963,13 +958,13 @@ int enqueue_round(prgpu_scene* s, prgpu_scene::Group& g, uint32_t iter_end)
 		g.shadow_pending = false;
 	}
 	if (g.n_active) {
-		s->time_begin(2, st);
+		s->time_begin(FAM_SHADE, st);
 		prd::launch_shade(s->sc, g.ps, g.active, g.slot_begin, g.n_active, g.next, g.counters, g.dead_cur, g.ws_closest.queue_head,
 						  g.ws_shadow.queue_head, s->gstats, st);
 		s->time_end(st);
 	}
 	if (g.n_dead_prev) {
-		s->time_begin(0, st);
+		s->time_begin(FAM_RAYGEN, st);
 		prd::launch_regen(s->sc, g.ps, g.dead_prev, g.n_dead_prev, iter_end, g.next, g.counters, s->gstats, st);
 		s->time_end(st);
 	}
@@ -985,7 +980,7 @@ int render_streaming(prgpu_scene* s, uint32_t iter_begin, uint32_t iter_end)
 		g.done = true;
 		if (!g.n_slots)
 			continue;
-		s->time_begin(0, g.s_main);
+		s->time_begin(FAM_RAYGEN, g.s_main);
 		prd::launch_raygen(s->sc, g.ps, g.slot_begin, g.n_slots, iter_begin, s->gstats, g.s_main);
 		s->time_end(g.s_main);
 		g.active		 = nullptr;
@@ -1017,7 +1012,7 @@ int render_streaming(prgpu_scene* s, uint32_t iter_begin, uint32_t iter_end)
 			const uint32_t n_dead	= g.n_active ? g.h_counters[2] : 0;
 			if (n_shadow && g.n_active) {
 				HIP_TRY(hipStreamWaitEvent(g.s_shadow, g.ev_shade, 0));
-				s->time_begin(3, g.s_shadow);
+				s->time_begin(FAM_TRACE_ANY, g.s_shadow);
 				prd::launch_trace_shadow(s->sc, g.ps, n_shadow, s->instrument, g.ws_shadow, s->gstats, g.s_shadow);
 				s->time_end(g.s_shadow);
 				HIP_TRY(hipEventRecord(g.ev_shadow, g.s_shadow));
@@ -1063,15 +1058,16 @@ int render_streaming(prgpu_scene* s, uint32_t iter_begin, uint32_t iter_end)
 // ---- persistent mode ------------------------------------------------------------------------------------------
 // One launch per render call: see k_path_persistent (device/render.hip).  Same per-pixel arithmetic and fragment order as
 // the other two modes, hence identical images.
-// The latency organisation runs a scene when the knob asks for it, or (auto) when the tile share is small enough that every owned pixel
-// is in flight at once in it -- and the library holds that variant of it, and the throughput kernel was not built one block per CU.
+// The latency organisation runs a scene only when PRGPU_PP_KERNEL=latency asks for it -- and the library holds that variant of it, and the
+// throughput kernel was not built one block per CU (else the throughput kernel runs, silently).  `auto` never selects it: on the small tile
+// shares it was made for it measured equal below 66 k pixels and 1.3 - 2.5 x slower above.
 bool use_latency_kernel(const prgpu_scene* s)
 {
 	if (s->knobs.pp_kernel == 1 || prd::persistent_block_threads() != 256u || !prd::latency_variant_built(s->sc.features))
 		return false;
 	if (s->knobs.pp_kernel == 2)
 		return true;
-	return false; // auto: decided by measurement
+	return false; // auto
 }
 
 int render_persistent(prgpu_scene* s, uint32_t iter_begin, uint32_t iter_end)
@@ -1097,9 +1093,7 @@ int render_persistent(prgpu_scene* s, uint32_t iter_begin, uint32_t iter_end)
 	// with fuller passes (C5 + 7 %, C4 - 10 %: profiles/r04_knobs.log).  The first launch of a scene therefore runs the INSTRUMENTED variant
 	// of the kernel (same results; it times its shading passes), and later launches use round(4 * share) shading waves, at most two.
 	// (Two clock reads per pass in the plain kernel were measured instead: 4 % slower on C4 -- the timers' scalar registers spill.)
-	// Which organisation of the kernel (render.h): the latency one for tile shares whose pixels are about as many as the chip's lanes
-	// (every pixel in flight at once in both organisations: a launch lasts as long as its deepest pixel's chain of vertices), the
-	// throughput one for everything larger.  PRGPU_PP_KERNEL fixes the choice (tests run both against the checker).
+	// Which organisation of the kernel (render.h): the throughput one unless PRGPU_PP_KERNEL=latency (tests run both against the checker).
 	const bool latency = use_latency_kernel(s);
 	const bool calibrating = s->knobs.pp.shader_wave < 0 && !all_in_flight && !latency;
 	auto decide = [&]() -> int { // after a calibration launch: read its timers (the launch's own: copies of the counters taken around it)
@@ -1137,7 +1131,7 @@ int render_persistent(prgpu_scene* s, uint32_t iter_begin, uint32_t iter_end)
 		const size_t gbytes = sizeof(unsigned long long) * prd::N_DEVICE_COUNTERS;
 		if (calibration) // the launch's counters = a copy of them after it minus a copy before it, both taken on the stream
 			HIP_TRY(hipMemcpyAsync(s->gstats_before, s->gstats, gbytes, hipMemcpyDeviceToDevice, s->stream));
-		s->time_begin(6, s->stream);
+		s->time_begin(FAM_PATH, s->stream);
 		if (latency)
 			prd::launch_path_latency(s->sc, ps, s->ps.pixel, s->n_slots, b, e, s->instrument, s->ws_pp, s->knobs.pl, s->pp_error, s->gstats, s->stream);
 		else
@@ -1166,7 +1160,7 @@ int render_persistent(prgpu_scene* s, uint32_t iter_begin, uint32_t iter_end)
 			prd::PathState pr = s->ps;
 			for (uint32_t i = b; i < e; ++i) {
 				pr.iter_xyz = s->ps.iter_xyz + size_t(i - b) * ps.plane_stride;
-				s->time_begin(4, s->stream);
+				s->time_begin(FAM_RESOLVE, s->stream);
 				prd::launch_resolve(s->sc, pr, i, s->stream);
 				s->time_end(s->stream);
 			}
@@ -1644,7 +1638,7 @@ int prgpu_trace_closest(prgpu_scene* s, uint32_t n, const float* org, const floa
 	TRY_OR_CLEAN(hipMemcpyAsync(d_dir, dir, size_t(n) * 12, hipMemcpyHostToDevice, s->stream));
 	TRY_OR_CLEAN(hipMemcpyAsync(d_tmin, tmin, size_t(n) * 4, hipMemcpyHostToDevice, s->stream));
 	TRY_OR_CLEAN(hipMemcpyAsync(d_tmax, tmax, size_t(n) * 4, hipMemcpyHostToDevice, s->stream));
-	s->time_begin(1, s->stream);
+	s->time_begin(FAM_TRACE_CLOSEST, s->stream);
 	// closest-hit service rays take the split traversal (leaf tests through an LDS task queue: identical results, 17 % faster) unless
 	// PRGPU_TRACE_SPLIT=0 or the tree has too many records for the 24-bit task field
 	const bool split = read_knobs().trace_split;
@@ -1694,7 +1688,7 @@ int prgpu_trace_any(prgpu_scene* s, uint32_t n, const float* org, const float* d
 	TRY_OR_CLEAN(hipMemcpyAsync(d_dir, dir, size_t(n) * 12, hipMemcpyHostToDevice, s->stream));
 	TRY_OR_CLEAN(hipMemcpyAsync(d_tmin, tmin, size_t(n) * 4, hipMemcpyHostToDevice, s->stream));
 	TRY_OR_CLEAN(hipMemcpyAsync(d_dist, distance, size_t(n) * 4, hipMemcpyHostToDevice, s->stream));
-	s->time_begin(3, s->stream);
+	s->time_begin(FAM_TRACE_ANY, s->stream);
 	prd::launch_service_any(s->sc, n, d_org, d_dir, d_tmin, d_dist, d_occ, s->ws, s->gstats, s->stream);
 	s->time_end(s->stream);
 	s->rays_any += n;
@@ -1923,7 +1917,7 @@ int prgpu_reduce(prgpu_scene* s, prgpu_comm* c, int root)
 			first_what	= what;
 		}
 	};
-	s->time_begin(7, s->stream);
+	s->time_begin(FAM_REDUCE, s->stream);
 	reduce(s->ps.out_xyz, is_root ? R.xyz : s->ps.out_xyz, size_t(s->n_pixels) * 3, NCCL_FLOAT32, NCCL_SUM, "ncclReduce(xyz)");
 	reduce(s->ps.samples, is_root ? R.samples : s->ps.samples, size_t(s->n_pixels), NCCL_UINT32, NCCL_SUM, "ncclReduce(samples)");
 	reduce(s->ps.feedback, is_root ? R.feedback : s->ps.feedback, size_t(s->n_pixels), NCCL_UINT32, NCCL_MAX, "ncclReduce(feedback)");
