@@ -28,37 +28,6 @@ __device__ __forceinline__ V3 uniform_hemi(float u1, float u2)
 	return v3(sinTheta * c, sinTheta * s, u1);
 }
 
-// RenderTileSession::pushSPFragment (:55): the pixel's sample count and, when enabled, the shading-point AOV sums (LocalFrameOutputDevice::
-// commitShadingPoints, LocalFrameOutputDevice.cpp:252-283) -- what shade_vertex does at the first vertex of a `direct` path, statement for statement
-// (kept apart from it: the persistent path kernels' translation units are not touched by this integrator)
-__device__ __forceinline__ void commit_shading_point(const PathState& ps, uint32_t pixel, V3 P, const GeomPoint& gp, V3 ray_d, float depth2)
-{
-	ps.samples[pixel] += 1;
-	if (ps.aov_mask) {
-		auto add3 = [&](int k, V3 v) {
-			if (ps.aov[k]) {
-				ps.aov[k][3 * pixel] += v.x;
-				ps.aov[k][3 * pixel + 1] += v.y;
-				ps.aov[k][3 * pixel + 2] += v.z;
-			}
-		};
-		auto add1 = [&](int k, float v) {
-			if (ps.aov[k])
-				ps.aov[k][pixel] += v;
-		};
-		add3(PRGPU_AOV_POSITION, P);
-		add3(PRGPU_AOV_NORMAL, gp.N);
-		add3(PRGPU_AOV_NORMAL_G, gp.N); // IntersectionPoint::setForSurface: Surface.N = Geometry.N (IntersectionPoint.h:61-75)
-		add3(PRGPU_AOV_TANGENT, gp.Nx);
-		add3(PRGPU_AOV_BITANGENT, gp.Ny);
-		add3(PRGPU_AOV_VIEW, ray_d);
-		add1(PRGPU_AOV_ENTITY_ID, (float)gp.entity);
-		add1(PRGPU_AOV_MATERIAL_ID, (float)gp.material);
-		add1(PRGPU_AOV_EMISSION_ID, (float)gp.emission);
-		add1(PRGPU_AOV_DEPTH, sqrtf(depth2));
-	}
-}
-
 // The camera rays' hits: handleShadingGroup up to the sample loop (ambientocclusion.cpp:33-38) and onTile's background branch (:68-69).
 template <bool INSTR>
 __global__ void __launch_bounds__(256) k_ao_hits(DevScene sc, PathState ps, AoState ao, uint32_t n_slots, uint32_t* __restrict__ n_hits /* zeroed by k_trace_closest */,
@@ -93,7 +62,7 @@ __global__ void __launch_bounds__(256) k_ao_hits(DevScene sc, PathState ps, AoSt
 			atomicAdd(&bs.v[PRGPU_STAT_CAMERA_DEPTH], 1u);
 			atomicAdd(&bs.v[PRGPU_STAT_SHADOW_RAYS], ao.sample_count);
 			const V3 dP = ray_o - P;
-			commit_shading_point(ps, pixel, P, gp, ray_d, dot(dP, dP)); // pushSPFragment (:55): per-pixel sums, their order against the colour fragment is free
+			commit_shading_point<true>(ps, pixel, P, gp, ray_d, dot(dP, dP)); // pushSPFragment (:55): per-pixel sums, their order against the colour fragment is free
 			const uint64_t state = ps.rng[pixel];
 			ps.rng[pixel]		 = state * ao.jump_all; // 2 N draws, whatever the rays find
 			if (INSTR)

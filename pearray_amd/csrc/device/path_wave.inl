@@ -76,6 +76,7 @@ __device__ __forceinline__ void path_wave(const DevScene& sc, const PathState& p
 		pend[i]				  = 0u;
 		ps.pixel[slot0 + i]	  = INVALID;
 	}
+	// (the wavelength table in LDS: restated from path_persistent, render.hip)
 	const bool wl_in_lds = sc.wl_cdf_size >= 2u && sc.wl_cdf_size <= WL_LDS && sc.cfg.mapper == PRGPU_MAPPER_SPD_CMIS;
 	if (wl_in_lds)
 		for (uint32_t i = threadIdx.x; i < sc.wl_cdf_size; i += TRAV_BLOCK)
@@ -106,12 +107,8 @@ __device__ __forceinline__ void path_wave(const DevScene& sc, const PathState& p
 	}
 	// ---- from here on the wave is on its own ----
 	Stack st;
-	st.lds			= sh.stack + threadIdx.x;
-	st.spill_stride = gridDim.x * TRAV_BLOCK;
-	st.spill		= a.spill + (blockIdx.x * TRAV_BLOCK + threadIdx.x);
-	st.reset();
 	Trav s;
-	s.cur			  = REC_EMPTY;
+	trav_attach(s, st, sh.stack, a.spill);
 	s.any			  = false;
 	bool has_ray	  = false;
 	uint32_t my_entry = 0;
@@ -166,23 +163,11 @@ __device__ __forceinline__ void path_wave(const DevScene& sc, const PathState& p
 				if (q == cls)
 					sh_head[q] += n;
 			const uint32_t slot = slot0 + slot_l;
-			if (mine) { // the NEE fragment of the slot's previous vertex, now that its shadow ray has reported
-				const uint32_t pw = pend[slot_l];
-				if (pw & PP_SHADOW) {
-					const float4 x		 = ps.st[slot].sh_xyz;
-					const uint32_t fbs	 = __float_as_uint(x.w);
-					const uint32_t pixel = ps.pixel[slot];
-					if (pw & PP_VISIBLE) {
-						const float xyz[3] = { x.x, x.y, x.z };
-						apply_fragment(ps, pixel, iter_entry(ps, slot, pixel), fbs & 0xFFu, xyz, (FEATS & FEAT_LPE) ? (fbs >> 16) & 0xFu : 0u);
-					} else if ((fbs >> 8) & 0xFFu) {
-						ps.feedback[pixel] |= (fbs >> 8) & 0xFFu;
-					}
-				}
-			}
+			if (mine)
+				apply_deferred_nee<FEATS>(ps, slot, pend[slot_l]);
 			bool alive = false, want_shadow = false;
 			float4 sh_o = make_float4(0, 0, 0, 0), sh_d = sh_o, sh_xyz = sh_o;
-			if (regen_pass) {
+			if (regen_pass) { // (this dispatch is restated from path_persistent, render.hip)
 			} else if (NQ > 1 && cls == 1) { // wave-uniform: the body with the rough / principled closures
 				if (mine)
 					shade_vertex<FEATS>(sc, ps, slot, sh.bs, alive, want_shadow, sh_o, sh_d, sh_xyz, &hits[slot_l]);
@@ -200,12 +185,7 @@ __device__ __forceinline__ void path_wave(const DevScene& sc, const PathState& p
 				if (pixel != INVALID) {
 					iter  = ps.iter[slot];
 					index = a.slot_index[slot];
-					if (ps.cost)
-						ps.cost[pixel] += (ps.st[slot].flags & 0xFFu) + 1u;
-					if (!ps.plane_stride) {
-						const float v[3] = { ps.iter_xyz[3 * pixel], ps.iter_xyz[3 * pixel + 1], ps.iter_xyz[3 * pixel + 2] };
-						fold_iteration(ps, pixel, iter, v, (FEATS & FEAT_LPE) != 0u);
-					}
+					fold_ended_sample<FEATS>(ps, slot, pixel, iter);
 					if (iter + 1 < a.iter_end) {
 						iter	   = iter + 1;
 						next_pixel = false;
@@ -289,7 +269,7 @@ __device__ __forceinline__ void path_wave(const DevScene& sc, const PathState& p
 			if (COUNT && lane == 0)
 				++witers;
 			const bool do_inner = n_inner >= n_leaf;
-			if (lane_in(do_inner ? m_inner : m_leaf)) {
+			if (lane_in(do_inner ? m_inner : m_leaf)) { // (this step and the counter flush at the end are restated from path_persistent, render.hip: see there)
 				const float4* __restrict__ rec = rec_ptr(sc.recs, s.cur);
 				const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2];
 				const bool wide = sc.bvh_wide != 0u;
@@ -323,7 +303,7 @@ __device__ __forceinline__ void path_wave(const DevScene& sc, const PathState& p
 				int qcls	   = 0;
 				if (fin) {
 					const uint32_t slot_l = my_entry & ~PP_ANY;
-					uint32_t add		  = 0xFFFFFFFFu; // -1
+					uint32_t add		  = 0xFFFFFFFFu; // -1 (the report word and the last / qcls decision below are restated from path_persistent, render.hip)
 					if (s.any) {
 						if (s.best.tri == INVALID)
 							add += PP_VISIBLE;

@@ -131,6 +131,16 @@ struct Trav {
 	uint32_t cls; // material class of the best hit's triangle (leaf record, float 31); tracked only where the caller asks for it
 };
 
+// a persistent loop's lane before its first ray: an empty stack over the thread's columns of the block's LDS array and of the spill slab, nothing to step
+__device__ __forceinline__ void trav_attach(Trav& s, Stack& st, uint2* lds_base, uint2* spill)
+{
+	st.lds			= lds_base + threadIdx.x;
+	st.spill_stride = gridDim.x * TRAV_BLOCK;
+	st.spill		= spill + (blockIdx.x * TRAV_BLOCK + threadIdx.x);
+	st.reset();
+	s.cur = REC_EMPTY;
+}
+
 // traversal flavour: closest hit, occlusion (any hit), or a per-lane mix of both in one wave (persistent path kernel)
 enum { MODE_CLOSEST = 0, MODE_ANY = 1, MODE_MIXED = 2 };
 
@@ -354,12 +364,8 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, uint32_t n_
 {
 	__shared__ uint2 lds_stack[STACK_LDS * TRAV_BLOCK];
 	Stack st;
-	st.lds			= lds_stack + threadIdx.x;
-	st.spill_stride = gridDim.x * TRAV_BLOCK;
-	st.spill		= spill + (blockIdx.x * TRAV_BLOCK + threadIdx.x);
-	st.reset();
 	Trav s;
-	s.cur			   = REC_EMPTY;
+	trav_attach(s, st, lds_stack, spill);
 	uint32_t my_ray	   = 0;
 	bool has_ray	   = false;
 	bool exhausted	   = false; // wave-uniform: the queue has no more rays
@@ -1627,6 +1633,38 @@ __device__ __forceinline__ uint32_t scatter_symbol(const prgpu_material& m, V3 V
 	}
 }
 
+// RenderTileSession::pushSPFragment (:55) of a path's first vertex (shade_vertex, and k_ao_hits of the `ao` integrator): the pixel's sample
+// count and, in kernels that hold the AOV code, the shading-point sums (LocalFrameOutputDevice::commitShadingPoints,
+// LocalFrameOutputDevice.cpp:252-283): plain per-pixel sums
+template <bool AOVS>
+__device__ __forceinline__ void commit_shading_point(const PathState& ps, uint32_t pixel, V3 P, const GeomPoint& gp, V3 ray_d, float depth2)
+{
+	ps.samples[pixel] += 1;
+	if (AOVS && ps.aov_mask) {
+		auto add3 = [&](int k, V3 v) {
+			if (ps.aov[k]) {
+				ps.aov[k][3 * pixel] += v.x;
+				ps.aov[k][3 * pixel + 1] += v.y;
+				ps.aov[k][3 * pixel + 2] += v.z;
+			}
+		};
+		auto add1 = [&](int k, float v) {
+			if (ps.aov[k])
+				ps.aov[k][pixel] += v;
+		};
+		add3(PRGPU_AOV_POSITION, P);
+		add3(PRGPU_AOV_NORMAL, gp.N);
+		add3(PRGPU_AOV_NORMAL_G, gp.N); // IntersectionPoint::setForSurface: Surface.N = Geometry.N (IntersectionPoint.h:61-75)
+		add3(PRGPU_AOV_TANGENT, gp.Nx);
+		add3(PRGPU_AOV_BITANGENT, gp.Ny);
+		add3(PRGPU_AOV_VIEW, ray_d);
+		add1(PRGPU_AOV_ENTITY_ID, (float)gp.entity);
+		add1(PRGPU_AOV_MATERIAL_ID, (float)gp.material);
+		add1(PRGPU_AOV_EMISSION_ID, (float)gp.emission);
+		add1(PRGPU_AOV_DEPTH, sqrtf(depth2));
+	}
+}
+
 template <uint32_t FEATS>
 __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState& ps, uint32_t slot, BlockStats& bs, bool& alive, bool& want_shadow,
 											 float4& sh_o, float4& sh_d, float4& sh_xyz, const float4* hit_src = nullptr /* the slot's hit when it is not in ps.hit (latency kernel: LDS) */)
@@ -1735,32 +1773,8 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 		const uint32_t pathLength = depth + 1;
 		atomicAdd(&bs.v[PRGPU_STAT_ENTITY_HITS], 1u);
 		atomicAdd(&bs.v[PRGPU_STAT_CAMERA_DEPTH], 1u);
-		if (pathLength == 1) {
-			ps.samples[pixel] += 1;
-			if ((FEATS & FEAT_AOVS) && ps.aov_mask) { // LocalFrameOutputDevice::commitShadingPoints (LocalFrameOutputDevice.cpp:252-283): plain per-pixel sums
-				auto add3 = [&](int k, V3 v) {
-					if (ps.aov[k]) {
-						ps.aov[k][3 * pixel] += v.x;
-						ps.aov[k][3 * pixel + 1] += v.y;
-						ps.aov[k][3 * pixel + 2] += v.z;
-					}
-				};
-				auto add1 = [&](int k, float v) {
-					if (ps.aov[k])
-						ps.aov[k][pixel] += v;
-				};
-				add3(PRGPU_AOV_POSITION, P);
-				add3(PRGPU_AOV_NORMAL, N);
-				add3(PRGPU_AOV_NORMAL_G, N); // IntersectionPoint::setForSurface: Surface.N = Geometry.N (IntersectionPoint.h:61-75)
-				add3(PRGPU_AOV_TANGENT, gp.Nx);
-				add3(PRGPU_AOV_BITANGENT, gp.Ny);
-				add3(PRGPU_AOV_VIEW, ray_d);
-				add1(PRGPU_AOV_ENTITY_ID, (float)gp.entity);
-				add1(PRGPU_AOV_MATERIAL_ID, (float)gp.material);
-				add1(PRGPU_AOV_EMISSION_ID, (float)gp.emission);
-				add1(PRGPU_AOV_DEPTH, sqrtf(depth2));
-			}
-		}
+		if (pathLength == 1)
+			commit_shading_point<(FEATS & FEAT_AOVS) != 0>(ps, pixel, P, gp, ray_d, depth2);
 		const bool hasEmission = gp.emission != INVALID;
 		bool go_on			   = true;
 		if (cfg.direct && hasEmission) {
@@ -2330,6 +2344,38 @@ __device__ __forceinline__ uint32_t ring_take(uint32_t* q, uint32_t cap_mask, ui
 	return v;
 }
 
+// ---- steps of one path that both organisations of the persistent kernel take (path_persistent below, path_wave in path_wave.inl), written once
+
+// the NEE fragment of the slot's previous vertex, now that its shadow ray has reported in the slot's pending word `pw` (see the end of the ray loop)
+template <uint32_t FEATS>
+__device__ __forceinline__ void apply_deferred_nee(const PathState& ps, uint32_t slot, uint32_t pw)
+{
+	if (pw & PP_SHADOW) {
+		const float4 x		 = ps.st[slot].sh_xyz;
+		const uint32_t fbs	 = __float_as_uint(x.w);
+		const uint32_t pixel = ps.pixel[slot];
+		if (pw & PP_VISIBLE) {
+			const float xyz[3] = { x.x, x.y, x.z };
+			apply_fragment(ps, pixel, iter_entry(ps, slot, pixel), fbs & 0xFFu, xyz, (FEATS & FEAT_LPE) ? (fbs >> 16) & 0xFu : 0u);
+		} else if ((fbs >> 8) & 0xFFu) {
+			ps.feedback[pixel] |= (fbs >> 8) & 0xFFu;
+		}
+	}
+}
+
+// a path has ended: its cost, and its sample into the pixel's running mean
+template <uint32_t FEATS>
+__device__ __forceinline__ void fold_ended_sample(const PathState& ps, uint32_t slot, uint32_t pixel, uint32_t iter)
+{
+	if (ps.cost)
+		ps.cost[pixel] += (ps.st[slot].flags & 0xFFu) + 1u;
+	if (!ps.plane_stride) { // single-tap filter: the sample folds into the running mean right here; with a ring of
+							// planes the launch only fills the planes and k_resolve gathers the taps afterwards
+		const float v[3] = { ps.iter_xyz[3 * pixel], ps.iter_xyz[3 * pixel + 1], ps.iter_xyz[3 * pixel + 2] };
+		fold_iteration(ps, pixel, iter, v, (FEATS & FEAT_LPE) != 0u);
+	}
+}
+
 
 struct PersistentArgs {
 	const uint32_t* owned; // Morton-ordered list of the pixels this device renders
@@ -2403,6 +2449,7 @@ __device__ __forceinline__ void path_persistent(const DevScene& sc, const PathSt
 			bl_list[i] = BL_UNWRITTEN;
 			bl_word[i] = 0u;
 		}
+	// (the wavelength table in LDS: restated in path_wave, path_wave.inl -- a shared form did not compile to the same code)
 	const bool wl_in_lds = sc.wl_cdf_size >= 2u && sc.wl_cdf_size <= WL_LDS && sc.cfg.mapper == PRGPU_MAPPER_SPD_CMIS;
 	if (wl_in_lds)
 		for (uint32_t i = threadIdx.x; i < sc.wl_cdf_size; i += TRAV_BLOCK)
@@ -2433,12 +2480,8 @@ __device__ __forceinline__ void path_persistent(const DevScene& sc, const PathSt
 	}
 
 	Stack st;
-	st.lds			= sh.stack + threadIdx.x;
-	st.spill_stride = gridDim.x * TRAV_BLOCK;
-	st.spill		= a.spill + (blockIdx.x * TRAV_BLOCK + threadIdx.x);
-	st.reset();
 	Trav s;
-	s.cur			  = REC_EMPTY;
+	trav_attach(s, st, sh.stack, a.spill);
 	s.any			  = false;
 	bool has_ray	  = false;
 	uint32_t my_entry = 0;
@@ -2501,24 +2544,12 @@ __device__ __forceinline__ void path_persistent(const DevScene& sc, const PathSt
 				if (mine)
 					slot_l = ring_take(sh.q_shade[cls], SHADE_MASK, first + lane);
 				const uint32_t slot = slot0 + slot_l;
-				if (mine) { // the NEE fragment of the slot's previous vertex, now that its shadow ray has reported (see the end of the ray loop)
-					const uint32_t pw = lds_load(&sh.pending[slot_l]);
-					if (pw & PP_SHADOW) {
-						const float4 x		 = ps.st[slot].sh_xyz;
-						const uint32_t fbs	 = __float_as_uint(x.w);
-						const uint32_t pixel = ps.pixel[slot];
-						if (pw & PP_VISIBLE) {
-							const float xyz[3] = { x.x, x.y, x.z };
-							apply_fragment(ps, pixel, iter_entry(ps, slot, pixel), fbs & 0xFFu, xyz, (FEATS & FEAT_LPE) ? (fbs >> 16) & 0xFu : 0u);
-						} else if ((fbs >> 8) & 0xFFu) {
-							ps.feedback[pixel] |= (fbs >> 8) & 0xFFu;
-						}
-					}
-				}
+				if (mine)
+					apply_deferred_nee<FEATS>(ps, slot, lds_load(&sh.pending[slot_l]));
 				bool alive = false, want_shadow = false;
 				float4 sh_o = make_float4(0, 0, 0, 0), sh_d = sh_o, sh_xyz = sh_o;
 				const unsigned long long t0v = COUNT ? wall_clock64() : 0ull;
-				if (regen_pass) {
+				if (regen_pass) { // (this dispatch is restated in path_wave, path_wave.inl)
 				} else if (NQ > 1 && cls == 1) { // wave-uniform: the body with the rough / principled closures
 					if (mine)
 						shade_vertex<FEATS>(sc, ps, slot, sh.bs, alive, want_shadow, sh_o, sh_d, sh_xyz);
@@ -2538,13 +2569,7 @@ __device__ __forceinline__ void path_persistent(const DevScene& sc, const PathSt
 					need_pixel			 = true;
 					if (pixel != INVALID) {
 						iter = ps.iter[slot];
-						if (ps.cost)
-							ps.cost[pixel] += (ps.st[slot].flags & 0xFFu) + 1u;
-						if (!ps.plane_stride) { // single-tap filter: the sample folds into the running mean right here; with a ring of
-												// planes the launch only fills the planes and k_resolve gathers the taps afterwards
-							const float v[3] = { ps.iter_xyz[3 * pixel], ps.iter_xyz[3 * pixel + 1], ps.iter_xyz[3 * pixel + 2] };
-							fold_iteration(ps, pixel, iter, v, (FEATS & FEAT_LPE) != 0u);
-						}
+						fold_ended_sample<FEATS>(ps, slot, pixel, iter);
 						if (iter + 1 < a.iter_end) {
 							if (!a.resident) { // the pixel's next sample follows in this slot
 								need_pixel = false;
@@ -2790,7 +2815,7 @@ __device__ __forceinline__ void path_persistent(const DevScene& sc, const PathSt
 			// records from the delayed shrinking of best.t, 1.5 % slower; 8-wide quantised nodes: 23 % fewer inner records, 2.5x the
 			// instructions per step, 13 % slower.)
 			const unsigned long long t0s = COUNT ? wall_clock64() : 0ull;
-			if (lane_in(do_inner ? m_inner : m_leaf)) {
+			if (lane_in(do_inner ? m_inner : m_leaf)) { // (this step and the counter flush at the end are restated in path_wave, path_wave.inl)
 				const float4* __restrict__ rec = rec_ptr(sc.recs, s.cur);
 				const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2]; // an inner record (48 of its 64 bytes are used in a 4-wide tree), or the start of a leaf
 				const bool wide = WIDE == 2 ? sc.bvh_wide != 0u : WIDE == 1;
@@ -2851,7 +2876,7 @@ __device__ __forceinline__ void path_persistent(const DevScene& sc, const PathSt
 					// is applied by the shading pass that takes the slot next -- same order (NEE of vertex k before anything of vertex k + 1),
 					// but the two dependent global round trips (fragment record, then the pixel's sums) no longer stall a wave full of rays
 					// in flight every time one of its shadow rays ends (a third of all rays; ~ 20 % of the traversal loop's time on C4).
-					uint32_t add = 0xFFFFFFFFu; // -1
+					uint32_t add = 0xFFFFFFFFu; // -1 (the report word and the last / qcls decision below are restated in path_wave, path_wave.inl)
 					if (s.any) {
 						if (s.best.tri == INVALID)
 							add += PP_VISIBLE;
