@@ -424,7 +424,7 @@ int  prgpu_download_primary_hits(prgpu_scene* s, uint32_t* entity, uint32_t* pri
 /* Time the traversal kernels alone on the rays recorded during the last iteration is not part of the
  * ABI; bench.py measures kernels with HIP events through prgpu_kernel_time_ms(). */
 /* Accumulated HIP-event time [ms] and launch count of a named kernel family since scene creation
- * ("trace_closest", "trace_any", "shade", "raygen", "resolve", "sort", "path", "reduce", "ao"). Requires prgpu_set_timing(s,1). */
+ * ("trace_closest", "trace_any", "shade", "raygen", "resolve", "sort", "path", "reduce", "ao", "vf"). Requires prgpu_set_timing(s,1). */
 int  prgpu_set_timing(prgpu_scene* s, int enabled);
 int  prgpu_kernel_time_ms(prgpu_scene* s, const char* family, double* total_ms, uint64_t* launches);
 
@@ -519,6 +519,36 @@ int prgpu_download_ao_counts(prgpu_scene* s, uint32_t* occluded);
  * and all-zero rays.  Any pointer may be NULL. */
 int prgpu_download_ao_samples(prgpu_scene* s, uint64_t* rng_state, float* org, float* dir, uint8_t* occluded);
 
+/* -- visual feedback integrator ----------------------------------------------------------------
+ * IntVFInstance (src/plugins/main/integrators/visualfeedback.cpp:108-250; `(integrator :type 'vf'|'visual'|'feedback'|'visual_feedback'|
+ * 'visualfeedback'|'debug' :mode ... :weighting true)`): the debug view of a camera sample's first hit.  A hit adds one fragment at unit
+ * importance whose radiance is a fixed colour at the sample's wavelengths times a quantity of the hit; a miss adds nothing; nothing is
+ * drawn from the pixel's generator after the camera sample; no shadow and no bounce rays.  With NdotV = dot(ray direction, N)
+ * (IntersectionPoint.h:71: negative for a front face, N never flipped) and weight = |NdotV|:
+ *   COLORED_ENTITY_ID / _MATERIAL_ID / _EMISSION_ID / _PRIMITIVE_ID  colour[id % 23] of 23 fixed colours (:56-80; prgpu_visual_feedback_color);
+ *                          an absent id is PRGPU_INVALID_ID, and 0xFFFFFFFF % 23 = 11
+ *   COLORED_DISPLACE_ID    colour 11 on every hit: no entity ever sets GeometryPoint::DisplaceID (GeometryPoint.h:24)
+ *   RAY_DIRECTION          red * a + green * b + blue * c, (a, b, c) = 0.5 * (direction + 1)
+ *   PARAMETER              red * u + green * v + blue * t: the intersector's hit parameters (u = v = 0 on spheres and quadrics)
+ *   INSIDE                 green for a back face (!signbit(NdotV)), red for a front face
+ *   NDOTV                  green * -NdotV for NdotV < 0, else red * NdotV; NEVER weighted
+ * and every mode but NDOTV multiplied by weight when `weighting` is non-zero.  The reference's colored_ray_id (a position in its ray
+ * stream) and validate_material ("most stuff is wrong", :212) are not built: the loader refuses them by name, PRGPU_EUNSUPPORTED.
+ * Enable before the first iteration: PRGPU_EINVAL afterwards, for a mode outside the enum, with the ambient occlusion integrator or
+ * light path expressions enabled, and twice; prgpu_enable_ambient_occlusion on such a scene is PRGPU_EINVAL too.  From then on
+ * prgpu_render runs an iteration-synchronous pipeline of its own (raygen, closest hits, ONE shading pass, resolve) for every pixel
+ * filter, whatever PRGPU_MODE says (prgpu_pipeline_info reports mode 0); tiles, AOVs, the variance planes, the tone mapper, outputs,
+ * the reduce, the primary-hit planes and the statistics work as for `direct` and `ao` -- camera depth counts EVERY camera sample,
+ * misses included (:243), which `ao` does not.  Light path expressions are not provided with it: prgpu_enable_lpe -- and
+ * prgpu_outputs_enable with an :lpe channel -- return PRGPU_EUNSUPPORTED on such a scene.  With prgpu_set_timing the shading pass is
+ * the kernel family "vf". */
+enum { PRGPU_VF_COLORED_ENTITY_ID = 0, PRGPU_VF_COLORED_MATERIAL_ID, PRGPU_VF_COLORED_EMISSION_ID, PRGPU_VF_COLORED_DISPLACE_ID,
+       PRGPU_VF_COLORED_PRIMITIVE_ID, PRGPU_VF_RAY_DIRECTION, PRGPU_VF_PARAMETER, PRGPU_VF_INSIDE, PRGPU_VF_NDOTV, PRGPU_VF_MODE_COUNT };
+int prgpu_enable_visual_feedback(prgpu_scene* s, uint32_t mode, int weighting);
+/* RGB of the integrator's fixed colours (host only): index 0 .. 22 the colours an id selects, 23 green (= true), 24 red (= false),
+ * 25 blue; PRGPU_EINVAL beyond.  prgpu_rgb_to_coeffs of it is what the shading pass evaluates. */
+int prgpu_visual_feedback_color(uint32_t index, float rgb[3]);
+
 /* Scheduling statistic of the persistent pipeline: path vertices traced per pixel so far (W*H u32; kept only while every owned pixel is in
  * flight at once -- a small tile share --, 0 otherwise and in the other pipelines).  The
  * backend uses it to hand the pixels with the longest sample chains to the fastest blocks of a small tile share; exposed for
@@ -574,7 +604,7 @@ int prgpu_write_exr(const char* path, uint32_t width, uint32_t height, uint32_t 
 /* -- .prc scene files ---------------------------------------------------------------------
  * Replaces SceneLoader::loadFromFile / loadFromString (src/loader/SceneLoader.cpp:44-72) for the part of the scene language the
  * `direct` hot path evaluates: (scene :render_width :render_height :camera :spectral_domain :spectral_hero), (sampler), (filter),
- * (spectral_mapper), (integrator :type 'direct'|'ao'), (camera :type 'standard'), (material :type 'diffuse'), (emission :type 'standard'),
+ * (spectral_mapper), (integrator :type 'direct'|'ao'|'vf'), (camera :type 'standard'), (material :type 'diffuse'), (emission :type 'standard'),
  * spectral expressions number / (refl r g b) / (illum r g b) / (illuminant "D65") / (spectrum :start :end v...) / (smul a b),
  * inline (mesh (attribute :type 'p'|'n' ...) (faces ...) (materials ...)), (entity :type 'mesh' ...), (include "file"),
  * (light :type 'env'|'distant'|'sun'|'sky') -- the sky's Hosek-Wilkie table is built by the loader (prgpu_sky_table).
@@ -592,7 +622,7 @@ typedef struct prgpu_prc_sky {
 typedef struct prgpu_prc_options {
 	uint32_t width, height; /* 0: keep :render_width / :render_height */
 	uint32_t aa_samples;    /* 0: keep the aa sampler's :sample_count */
-	uint32_t force_direct;  /* 1: accept any (integrator :type ...) and render it with `direct` at default parameters (`ao` included) */
+	uint32_t force_direct;  /* 1: accept any (integrator :type ...) and render it with `direct` at default parameters (`ao` and `vf` included) */
 	uint64_t seed;          /* 0: RenderSettings default (42) */
 	uint32_t n_skies;       /* host-supplied sky tables (may be 0: the loader builds them) */
 	uint32_t reserved;
@@ -621,11 +651,17 @@ int prgpu_prc_load_file(const char* path, const prgpu_prc_options* options, prgp
 int prgpu_prc_load_string(const char* source, const char* include_dir, const prgpu_prc_options* options, prgpu_prc** out);
 const prgpu_scene_desc* prgpu_prc_desc(const prgpu_prc* scene);
 const char* prgpu_prc_warnings(const prgpu_prc* scene); /* newline separated */
-/* The scene's (integrator ...) block: PRGPU_INTEGRATOR_DIRECT (also without a block, and for every type under force_direct) or
- * PRGPU_INTEGRATOR_AO with its :sample_count (default 10; 0 for `direct`).  A host renders an AO scene by calling
- * prgpu_enable_ambient_occlusion(scene, ao_sample_count) after prgpu_scene_create.  Either output pointer may be NULL. */
-enum { PRGPU_INTEGRATOR_DIRECT = 0, PRGPU_INTEGRATOR_AO = 1 };
+/* The scene's (integrator ...) block: PRGPU_INTEGRATOR_DIRECT (also without a block, and for every type under force_direct),
+ * PRGPU_INTEGRATOR_AO with its :sample_count (default 10; 0 for the others) or PRGPU_INTEGRATOR_VF.  A host renders an AO scene by calling
+ * prgpu_enable_ambient_occlusion(scene, ao_sample_count) after prgpu_scene_create, a VF scene by calling prgpu_enable_visual_feedback
+ * with what prgpu_prc_visual_feedback reports.  Either output pointer may be NULL. */
+enum { PRGPU_INTEGRATOR_DIRECT = 0, PRGPU_INTEGRATOR_AO = 1, PRGPU_INTEGRATOR_VF = 2 };
 int prgpu_prc_integrator(const prgpu_prc* scene, uint32_t* kind, uint32_t* ao_sample_count);
+/* :mode (PRGPU_VF_*) and :weighting (default true) of a PRGPU_INTEGRATOR_VF scene; PRGPU_EINVAL for any other scene.  Mode names are
+ * case-insensitive; a MISSING :mode is colored_entity_id, as in the reference (visualfeedback.cpp:50,291-301: the lookup table ends in
+ * { "", ColoredEntityID } and its end test never fires) and not `parameter` as its plugin specification says; an unknown name, and the
+ * two modes that are not built, fail the load with PRGPU_EUNSUPPORTED and the name.  Either output pointer may be NULL. */
+int prgpu_prc_visual_feedback(const prgpu_prc* scene, uint32_t* mode, int* weighting);
 /* What the SkyModel of light `light` (a PRGPU_LIGHT_SKY of the loaded scene) was built from; PRGPU_EINVAL for any other light. */
 int prgpu_prc_sky_info(const prgpu_prc* scene, uint32_t light, prgpu_sky_params* out);
 /* The scene's (output ...) blocks: their channels (all files, in file order) and the :name of file k (NULL beyond the last). */

@@ -32,7 +32,12 @@ SAMPLER_RANDOM, SAMPLER_MJITT, SAMPLER_SOBOL, SAMPLER_HALTON, SAMPLER_HAMMERSLEY
 MAPPER_SPD_CMIS, MAPPER_RANDOM, MAPPER_SPD_HERO, MAPPER_CIE, MAPPER_CIE_Y, MAPPER_AGH_CMIS, MAPPER_AGH_HERO = range(7)
 FILTER_BLOCK, FILTER_TRIANGLE, FILTER_GAUSSIAN, FILTER_MITCHELL, FILTER_LANCZOS = range(5)
 MIS_BALANCE, MIS_POWER = range(2)
-INTEGRATOR_DIRECT, INTEGRATOR_AO = range(2)
+INTEGRATOR_DIRECT, INTEGRATOR_AO, INTEGRATOR_VF = range(3)
+# modes of the visual feedback integrator (PRGPU_VF_*), in the order of the enum; VF_MODES[name] -> number
+VF_MODE_NAMES = ("colored_entity_id", "colored_material_id", "colored_emission_id", "colored_displace_id", "colored_primitive_id",
+                 "ray_direction", "parameter", "inside", "ndotv")
+VF_MODES = {name: k for k, name in enumerate(VF_MODE_NAMES)}
+VF_COLOR_GREEN, VF_COLOR_RED, VF_COLOR_BLUE = 23, 24, 25   # rows of prgpu_visual_feedback_color after the 23 id colours
 
 STAT_NAMES = ("camera_rays", "light_rays", "primary_rays", "bounce_rays", "shadow_rays", "monochrome_rays",
               "pixel_samples", "entity_hits", "background_hits", "camera_depth", "light_depth")
@@ -195,6 +200,8 @@ SYMBOLS = {
     "prgpu_download_variance": (C.c_int, [_VP, _F32P, _F32P]),
     "prgpu_path_cost": (C.c_int, [_VP, _U32P]),
     "prgpu_enable_ambient_occlusion": (C.c_int, [_VP, C.c_uint32]),
+    "prgpu_enable_visual_feedback": (C.c_int, [_VP, C.c_uint32, C.c_int]),
+    "prgpu_visual_feedback_color": (C.c_int, [C.c_uint32, _F32P]),
     "prgpu_download_ao_counts": (C.c_int, [_VP, _U32P]),
     "prgpu_download_ao_samples": (C.c_int, [_VP, _U64P, _F32P, _F32P, _U8P]),
     "prgpu_lpe_check": (C.c_int, [C.c_char_p]),
@@ -221,6 +228,7 @@ SYMBOLS = {
     "prgpu_prc_desc": (C.POINTER(SceneDesc), [_VP]),
     "prgpu_prc_warnings": (C.c_char_p, [_VP]),
     "prgpu_prc_integrator": (C.c_int, [_VP, _U32P, _U32P]),
+    "prgpu_prc_visual_feedback": (C.c_int, [_VP, _U32P, C.POINTER(C.c_int)]),
     "prgpu_prc_last_error": (C.c_char_p, []),
     "prgpu_prc_free": (None, [_VP]),
 }

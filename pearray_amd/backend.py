@@ -35,6 +35,9 @@ class RenderContext:
         self.ao_sample_count = 0
         if getattr(scene, "integrator", abi.INTEGRATOR_DIRECT) == abi.INTEGRATOR_AO:   # (integrator :type 'ao') / SceneBuilder.ambient_occlusion
             self.enableAmbientOcclusion(scene.ao_sample_count)
+        self.vf_mode = None
+        if getattr(scene, "integrator", abi.INTEGRATOR_DIRECT) == abi.INTEGRATOR_VF:   # (integrator :type 'vf') / SceneBuilder.visual_feedback
+            self.enableVisualFeedback(scene.vf_mode, scene.vf_weighting)
 
     def close(self):
         if self._h:
@@ -159,6 +162,14 @@ class RenderContext:
         per camera sample that hits a surface; enable before the first iteration."""
         abi.check(self.lib.prgpu_enable_ambient_occlusion(self._h, int(sample_count)))
         self.ao_sample_count = int(sample_count)
+
+    def enableVisualFeedback(self, mode, weighting=True):
+        """Render with the visual feedback integrator (visualfeedback.cpp:108-250) instead of `direct`: `mode` is a PRGPU_VF_* number or
+        its name (abi.VF_MODE_NAMES), `weighting` multiplies every mode but `ndotv` by |N.V|; enable before the first iteration."""
+        if isinstance(mode, str):
+            mode = abi.VF_MODES[mode.lower()]
+        abi.check(self.lib.prgpu_enable_visual_feedback(self._h, int(mode), 1 if weighting else 0))
+        self.vf_mode, self.vf_weighting = int(mode), bool(weighting)
 
     def aoCounts(self):
         """Occluded rays per pixel over all iterations so far, uint32 [H, W]."""

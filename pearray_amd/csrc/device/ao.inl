@@ -28,7 +28,8 @@ __device__ __forceinline__ V3 uniform_hemi(float u1, float u2)
 	return v3(sinTheta * c, sinTheta * s, u1);
 }
 
-// The camera rays' hits: handleShadingGroup up to the sample loop (ambientocclusion.cpp:33-38) and onTile's background branch (:68-69).
+// The camera rays' hits: handleShadingGroup up to the sample loop (ambientocclusion.cpp:33-38) and onTile's background branch (:68-69) --
+// camera_vertex (render.hip), which k_vf_shade shares -- and the hit's record.
 template <bool INSTR>
 __global__ void __launch_bounds__(256) k_ao_hits(DevScene sc, PathState ps, AoState ao, uint32_t n_slots, uint32_t* __restrict__ n_hits /* zeroed by k_trace_closest */,
 												 uint32_t* queue_head_closest, uint32_t* queue_head_ao, unsigned long long* gstats)
@@ -42,37 +43,22 @@ __global__ void __launch_bounds__(256) k_ao_hits(DevScene sc, PathState ps, AoSt
 	const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
 	bool hit			= false;
 	float4 r0 = make_float4(0, 0, 0, 0), r1 = r0, r2 = r0, r3 = r0;
-	if (slot < n_slots && !(ps.st[slot].flags & FLAG_NO_RAY)) { // (a sample the camera had no ray for is neither: camera_path, shade_vertex)
-		const uint32_t pixel = ps.pixel[slot];
-		const float4 hit4	 = ps.st[slot].hit;
-		const uint32_t tri	 = __float_as_uint(hit4.w);
-		if (tri == INVALID) {
-			ps.prim_entity[pixel] = INVALID;
-			ps.prim_prim[pixel]	  = INVALID;
-			atomicAdd(&bs.v[PRGPU_STAT_BACKGROUND_HITS], 1u);
-		} else {
-			const float4 ro = ps.st[slot].ray_o, rd = ps.st[slot].ray_d;
-			const V3 ray_o = v3(ro.x, ro.y, ro.z), ray_d = v3(rd.x, rd.y, rd.z);
-			const V3 P = ray_o + ray_d * hit4.x;
-			GeomPoint gp;
-			geometry_point<(FEAT_ALL & ~FEAT_LPE)>(sc, tri, hit4.y, hit4.z, P, gp); // (every branch compiled in: which one runs is the entity's business)
-			ps.prim_entity[pixel] = gp.entity;
-			ps.prim_prim[pixel]	  = gp.prim;
-			atomicAdd(&bs.v[PRGPU_STAT_ENTITY_HITS], 1u);
-			atomicAdd(&bs.v[PRGPU_STAT_CAMERA_DEPTH], 1u);
-			atomicAdd(&bs.v[PRGPU_STAT_SHADOW_RAYS], ao.sample_count);
-			const V3 dP = ray_o - P;
-			commit_shading_point<true>(ps, pixel, P, gp, ray_d, dot(dP, dP)); // pushSPFragment (:55): per-pixel sums, their order against the colour fragment is free
-			const uint64_t state = ps.rng[pixel];
-			ps.rng[pixel]		 = state * ao.jump_all; // 2 N draws, whatever the rays find
-			if (INSTR)
-				ao.dbg_state[pixel] = state;
-			r0	= make_float4(P.x, P.y, P.z, __uint_as_float(slot));
-			r1	= make_float4(gp.N.x, gp.N.y, gp.N.z, __uint_as_float((uint32_t)state));
-			r2	= make_float4(gp.Nx.x, gp.Nx.y, gp.Nx.z, __uint_as_float((uint32_t)(state >> 32)));
-			r3	= make_float4(gp.Ny.x, gp.Ny.y, gp.Ny.z, 0.0f);
-			hit = true;
-		}
+	CameraVertex cv;
+	if (camera_vertex(sc, ps, slot, n_slots, bs, cv) == CV_HIT) { // (statistics of hit and background, geometry point, primary-hit planes, pushSPFragment (:55))
+		const uint32_t pixel = cv.pixel;
+		const V3 P			 = cv.P;
+		const GeomPoint& gp	 = cv.gp;
+		atomicAdd(&bs.v[PRGPU_STAT_CAMERA_DEPTH], 1u); // hits only (:34)
+		atomicAdd(&bs.v[PRGPU_STAT_SHADOW_RAYS], ao.sample_count);
+		const uint64_t state = ps.rng[pixel];
+		ps.rng[pixel]		 = state * ao.jump_all; // 2 N draws, whatever the rays find
+		if (INSTR)
+			ao.dbg_state[pixel] = state;
+		r0	= make_float4(P.x, P.y, P.z, __uint_as_float(slot));
+		r1	= make_float4(gp.N.x, gp.N.y, gp.N.z, __uint_as_float((uint32_t)state));
+		r2	= make_float4(gp.Nx.x, gp.Nx.y, gp.Nx.z, __uint_as_float((uint32_t)(state >> 32)));
+		r3	= make_float4(gp.Ny.x, gp.Ny.y, gp.Ny.z, 0.0f);
+		hit = true;
 	}
 	const uint32_t h = wave_append(hit, n_hits);
 	if (hit) {
@@ -143,13 +129,7 @@ __global__ void __launch_bounds__(256) k_ao_splat(DevScene sc, PathState ps, AoS
 	ao.counts[pixel] += occ;
 	const float weight	 = 1.0f - occ / (float)ao.sample_count;
 	const uint32_t flags = ps.st[slot].flags;
-	PathCie cie;
-	{
-		const float4 cx = ps.st[slot].cie_x, cy = ps.st[slot].cie_y, cz = ps.st[slot].cie_z;
-		cie.x[0] = cx.x; cie.x[1] = cx.y; cie.x[2] = cx.z; cie.x[3] = cx.w;
-		cie.y[0] = cy.x; cie.y[1] = cy.y; cie.y[2] = cy.z; cie.y[3] = cy.w;
-		cie.z[0] = cz.x; cie.z[1] = cz.y; cie.z[2] = cz.z; cie.z[3] = cz.w;
-	}
+	const PathCie cie  = slot_cie(ps, slot);
 	const Blob grp_imp = (flags & FLAG_GROUP_MONO) ? hero_only() : blob(1.0f); // RenderTile.cpp:126-127 (importance of the ray group)
 	float xyz[3];
 	const uint32_t fb = fragment_value(sc, blob(1), blob(1), grp_imp, blob(weight), (flags & FLAG_MONO) != 0, cie, 1.0f, xyz);

@@ -183,4 +183,15 @@ void launch_ao_occlusion(const DevScene& sc, const PathState& ps, const AoState&
 						 unsigned long long* gstats, hipStream_t st);
 void launch_ao_splat(const DevScene& sc, const PathState& ps, const AoState& ao, uint32_t n_slots, const uint32_t* n_hits, hipStream_t st);
 bool ao_counts_folded(); // how the occlusion kernel was built (PR_AO_FOLD): one atomic per hit and wave step, or one per occluded ray
+
+// Visual feedback pipeline (device/vf.inl): ONE pass between k_trace_closest and k_resolve of an iteration.
+// Rows of the colour table (tables/pr_vf_colors.inl): the 23 colours an id selects by id % 23, then green (= True), red (= False), blue.
+constexpr uint32_t VF_RANDOM_COLOURS = 23, VF_GREEN = 23, VF_RED = 24, VF_BLUE = 25, VF_COLOURS = 26;
+// What prgpu_enable_visual_feedback sets up; passed by value.
+struct VfState {
+	const float4* colours; // VF_COLOURS rows: the upsampler's three coefficients of the colour (prgpu_rgb_to_coeffs), w unused
+	uint32_t mode;		   // PRGPU_VF_*
+	uint32_t weighting;	   // radiance *= |NdotV| (every mode but PRGPU_VF_NDOTV)
+};
+void launch_vf_shade(const DevScene& sc, const PathState& ps, const VfState& vf, uint32_t n_slots, uint32_t* queue_head_closest, unsigned long long* gstats, hipStream_t st);
 } // namespace prd

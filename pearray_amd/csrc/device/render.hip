@@ -2973,7 +2973,57 @@ __global__ void __launch_bounds__(TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu
 #include "path_wave.inl"
 
 #if PR_UNIT == PR_WAVEFRONT
+// ---- what the iteration-synchronous integrators (`ao`: ao.inl, `vf`: vf.inl) share of a camera sample's first vertex --------------------
+// handleShadingGroup up to the integrator's own work (ambientocclusion.cpp:33-38, visualfeedback.cpp:112-117) and onTile's background
+// branch (ambientocclusion.cpp:68-69, visualfeedback.cpp:244-245): the hit / background statistics, the geometry point, the primary-hit
+// planes and pushSPFragment.  CameraDepthCount is the caller's: the two integrators count it differently.
+struct CameraVertex {
+	uint32_t pixel;
+	float4 hit4; // (t, u, v, triangle bits) of the closest hit
+	V3 ray_d, P;
+	GeomPoint gp;
+};
+enum { CV_NONE, CV_BACKGROUND, CV_HIT }; // CV_NONE: no slot, or a sample the camera had no ray for (camera_path, shade_vertex) -- neither hit nor background
+__device__ __forceinline__ int camera_vertex(const DevScene& sc, const PathState& ps, uint32_t slot, uint32_t n_slots, BlockStats& bs, CameraVertex& cv)
+{
+	if (slot >= n_slots || (ps.st[slot].flags & FLAG_NO_RAY))
+		return CV_NONE;
+	const uint32_t pixel = ps.pixel[slot];
+	const float4 hit4	 = ps.st[slot].hit;
+	const uint32_t tri	 = __float_as_uint(hit4.w);
+	cv.pixel			 = pixel;
+	cv.hit4				 = hit4;
+	if (tri == INVALID) {
+		ps.prim_entity[pixel] = INVALID;
+		ps.prim_prim[pixel]	  = INVALID;
+		atomicAdd(&bs.v[PRGPU_STAT_BACKGROUND_HITS], 1u);
+		return CV_BACKGROUND;
+	}
+	const float4 ro = ps.st[slot].ray_o, rd = ps.st[slot].ray_d;
+	const V3 ray_o = v3(ro.x, ro.y, ro.z), ray_d = v3(rd.x, rd.y, rd.z);
+	const V3 P = ray_o + ray_d * hit4.x;
+	geometry_point<(FEAT_ALL & ~FEAT_LPE)>(sc, tri, hit4.y, hit4.z, P, cv.gp); // (every branch compiled in: which one runs is the entity's business)
+	ps.prim_entity[pixel] = cv.gp.entity;
+	ps.prim_prim[pixel]	  = cv.gp.prim;
+	atomicAdd(&bs.v[PRGPU_STAT_ENTITY_HITS], 1u);
+	const V3 dP = ray_o - P;
+	commit_shading_point<true>(ps, pixel, P, cv.gp, ray_d, dot(dP, dP)); // pushSPFragment: per-pixel sums, their order against the colour fragment is free
+	cv.ray_d = ray_d;
+	cv.P	 = P;
+	return CV_HIT;
+}
+// the CIE responses raygen kept for the slot's four wavelengths
+__device__ __forceinline__ PathCie slot_cie(const PathState& ps, uint32_t slot)
+{
+	PathCie cie;
+	const float4 cx = ps.st[slot].cie_x, cy = ps.st[slot].cie_y, cz = ps.st[slot].cie_z;
+	cie.x[0] = cx.x; cie.x[1] = cx.y; cie.x[2] = cx.z; cie.x[3] = cx.w;
+	cie.y[0] = cy.x; cie.y[1] = cy.y; cie.y[2] = cy.z; cie.y[3] = cy.w;
+	cie.z[0] = cz.x; cie.z[1] = cz.y; cie.z[2] = cz.z; cie.z[3] = cz.w;
+	return cie;
+}
 #include "ao.inl"
+#include "vf.inl"
 
 // ---- ray service kernels (IArchive surface) ------------------------------------------------------------
 __global__ void __launch_bounds__(TRAV_BLOCK) k_service_closest(DevScene sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,
@@ -3408,6 +3458,10 @@ void launch_ao_splat(const DevScene& sc, const PathState& ps, const AoState& ao,
 	hipLaunchKernelGGL(k_ao_splat, grid_for(n_slots), dim3(256), 0, st, sc, ps, ao, n_hits);
 }
 bool ao_counts_folded() { return PR_AO_FOLD != 0; }
+void launch_vf_shade(const DevScene& sc, const PathState& ps, const VfState& vf, uint32_t n_slots, uint32_t* queue_head_closest, unsigned long long* gstats, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_vf_shade, grid_for(n_slots), dim3(256), 0, st, sc, ps, vf, n_slots, queue_head_closest, gstats);
+}
 
 #endif // PR_UNIT == PR_WAVEFRONT
 

@@ -50,6 +50,7 @@ struct prgpu_prc {
 	prgpu_scene_desc desc;
 	std::string warnings;
 	uint32_t integrator = PRGPU_INTEGRATOR_DIRECT, ao_sample_count = 0;
+	uint32_t vf_mode = 0, vf_weighting = 0; // PRGPU_INTEGRATOR_VF: its :mode (PRGPU_VF_*) and :weighting
 };
 
 namespace {
@@ -667,8 +668,39 @@ struct Loader {
 			have_integrator		= true; // (the `direct` parameters keep their defaults: nothing reads them)
 			return;
 		}
+		if ((type == "vf" || type == "visual" || type == "feedback" || type == "visual_feedback" || type == "visualfeedback" || type == "debug") && !opt.force_direct) { // visualfeedback.cpp:331
+			// IntVFFactory::createInstance (visualfeedback.cpp:291-301) looks the lower-cased :mode up in a table whose LAST row is { "", ColoredEntityID }
+			// (:50) and whose loop never meets its end test (`_mode[i].Name` of that row is a non-null pointer): a missing :mode is the empty string and
+			// selects colored_entity_id -- not `parameter`, the initial value (:295) and what the plugin specification (:345) claims --, and an unknown
+			// non-empty one reads past the table there: refused here.
+			static const struct {
+				const char* name;
+				int mode; // PRGPU_VF_*, or -1: a mode of the reference that is not built
+			} MODES[] = { { "colored_entity_id", PRGPU_VF_COLORED_ENTITY_ID }, { "colored_material_id", PRGPU_VF_COLORED_MATERIAL_ID },
+						  { "colored_emission_id", PRGPU_VF_COLORED_EMISSION_ID }, { "colored_displace_id", PRGPU_VF_COLORED_DISPLACE_ID },
+						  { "colored_primitive_id", PRGPU_VF_COLORED_PRIMITIVE_ID }, { "colored_ray_id", -1 }, { "ray_direction", PRGPU_VF_RAY_DIRECTION },
+						  { "parameter", PRGPU_VF_PARAMETER }, { "inside", PRGPU_VF_INSIDE }, { "ndotv", PRGPU_VF_NDOTV }, { "validate_material", -1 },
+						  { "", PRGPU_VF_COLORED_ENTITY_ID } };
+			const std::string mode = lower(get_string(g, "mode", ""));
+			int found			   = -2;
+			for (const auto& m : MODES)
+				if (mode == m.name) {
+					found = m.mode;
+					break;
+				}
+			if (found == -2)
+				fail(PRGPU_EUNSUPPORTED, where(g) + ": visual feedback :mode '" + mode + "' is not a mode of the integrator");
+			if (found == -1) // colored_ray_id: a position in the reference's ray stream, which has no counterpart here; validate_material: "most stuff is wrong" (:212)
+				fail(PRGPU_EUNSUPPORTED, where(g) + ": visual feedback :mode '" + mode + "' is not supported");
+			out.integrator		= PRGPU_INTEGRATOR_VF;
+			out.ao_sample_count = 0;
+			out.vf_mode			= (uint32_t)found;
+			out.vf_weighting	= get_bool(g, "weighting", true) ? 1u : 0u; // :302
+			have_integrator		= true; // (the `direct` parameters keep their defaults: nothing reads them)
+			return;
+		}
 		if (!direct && !opt.force_direct)
-			fail(PRGPU_EUNSUPPORTED, where(g) + ": integrator '" + type + "' is not supported (only direct/standard/default and ao/occlusion/ambient_occlusion; set force_direct to render with `direct` anyway)");
+			fail(PRGPU_EUNSUPPORTED, where(g) + ": integrator '" + type + "' is not supported (only direct/standard/default, ao/occlusion/ambient_occlusion and vf/visual/feedback/visual_feedback/visualfeedback/debug; set force_direct to render with `direct` anyway)");
 		if (!direct) {
 			warn(where(g) + ": integrator '" + type + "' replaced by 'direct' with default parameters (force_direct)");
 			have_integrator = true;
@@ -2013,6 +2045,7 @@ int load(const std::string& source, const std::string& dir, const prgpu_prc_opti
 		l.run(source, dir);
 	} catch (const LoadError& e) {
 		g_prc_error = e.msg;
+		prgpu_host::set_last_error(e.code, e.msg); // (prgpu_last_error names it too)
 		delete p;
 		return e.code;
 	} catch (const std::exception& e) {
@@ -2065,6 +2098,16 @@ int prgpu_prc_integrator(const prgpu_prc* p, uint32_t* kind, uint32_t* ao_sample
 		*kind = p->integrator;
 	if (ao_sample_count)
 		*ao_sample_count = p->ao_sample_count;
+	return PRGPU_OK;
+}
+int prgpu_prc_visual_feedback(const prgpu_prc* p, uint32_t* mode, int* weighting)
+{
+	if (!p || p->integrator != PRGPU_INTEGRATOR_VF)
+		return PRGPU_EINVAL;
+	if (mode)
+		*mode = p->vf_mode;
+	if (weighting)
+		*weighting = (int)p->vf_weighting;
 	return PRGPU_OK;
 }
 int prgpu_prc_sky_info(const prgpu_prc* p, uint32_t light, prgpu_sky_params* out)

@@ -19,6 +19,8 @@
 #include "device/bvh.h"
 #include "device/render.h"
 #include "host/setup.h"
+#include "tables/pr_vf_colors.inl"
+static_assert(sizeof(PR_VF_COLOR_RGB) / sizeof(PR_VF_COLOR_RGB[0]) == prd::VF_COLOURS, "one row per colour index of device/render.h");
 
 namespace {
 
@@ -174,8 +176,8 @@ struct TimedLaunch {
 	hipEvent_t start, stop;
 	int family;
 };
-enum Family { FAM_RAYGEN, FAM_TRACE_CLOSEST, FAM_SHADE, FAM_TRACE_ANY, FAM_RESOLVE, FAM_SORT, FAM_PATH, FAM_REDUCE, FAM_AO, N_FAMILIES };
-const char* const FAMILY_NAMES[] = { "raygen", "trace_closest", "shade", "trace_any", "resolve", "sort", "path", "reduce", "ao" }; // in the order of Family
+enum Family { FAM_RAYGEN, FAM_TRACE_CLOSEST, FAM_SHADE, FAM_TRACE_ANY, FAM_RESOLVE, FAM_SORT, FAM_PATH, FAM_REDUCE, FAM_AO, FAM_VF, N_FAMILIES };
+const char* const FAMILY_NAMES[] = { "raygen", "trace_closest", "shade", "trace_any", "resolve", "sort", "path", "reduce", "ao", "vf" }; // in the order of Family
 static_assert(sizeof(FAMILY_NAMES) / sizeof(FAMILY_NAMES[0]) == N_FAMILIES, "one name per timing family");
 
 } // namespace
@@ -245,6 +247,9 @@ struct prgpu_scene {
 	// ambient occlusion integrator (prgpu_enable_ambient_occlusion; device/ao.inl): its pipeline replaces the scene's mode for good
 	bool ao_enabled = false;
 	prd::AoState ao{};
+	// visual feedback integrator (prgpu_enable_visual_feedback; device/vf.inl): likewise, and never together with `ao`
+	bool vf_enabled = false;
+	prd::VfState vf{};
 	prd::TraceWorkspace ws_ao;		  // the occlusion launch: the ray service's grid
 	std::vector<prgpu_tile> tiles;	  // as last given to apply_tiles (enabling AO orders the owned pixels again: the order depends on the mode)
 	prd::DevLpe lpe_host{}; // host copy of the light path expression block (plane pointers for downloads and the reduce)
@@ -936,6 +941,31 @@ int render_ao_iteration(prgpu_scene* s, uint32_t iter)
 	return PRGPU_OK;
 }
 
+// ---- visual feedback ----------------------------------------------------------------------------------------------
+// One iteration of the VF pipeline (device/vf.inl) on the scene stream: camera rays and their closest hits as the lockstep pipeline's
+// first vertex, ONE pass that shades every slot, then the filter taps and the running mean.
+int render_vf_iteration(prgpu_scene* s, uint32_t iter)
+{
+	if (!s->n_slots)
+		return PRGPU_OK;
+	hipStream_t st		   = s->stream;
+	prgpu_scene::Group& g0 = s->groups[0]; // (its closest-hit workspace and counters, as render_ao_iteration)
+	s->time_begin(FAM_RAYGEN, st);
+	prd::launch_raygen(s->sc, s->ps, 0, s->n_slots, iter, s->gstats, st);
+	s->time_end(st);
+	s->time_begin(FAM_TRACE_CLOSEST, st);
+	prd::launch_trace_closest(s->sc, s->ps, nullptr, 0, s->n_slots, s->instrument, g0.ws_closest, g0.counters, s->gstats, st);
+	s->time_end(st);
+	s->time_begin(FAM_VF, st);
+	prd::launch_vf_shade(s->sc, s->ps, s->vf, s->n_slots, g0.ws_closest.queue_head, s->gstats, st);
+	s->time_end(st);
+	s->time_begin(FAM_RESOLVE, st);
+	prd::launch_resolve(s->sc, s->ps, iter, st);
+	s->time_end(st);
+	HIP_TRY(hipGetLastError());
+	return PRGPU_OK;
+}
+
 // ---- streaming mode ---------------------------------------------------------------------------------------------
 // Pixels advance through their samples independently: when a path ends, its pixel's sum is folded into the running
 // mean and the pixel's next camera path joins the wavefront in the following round (k_regen).  The wavefront therefore
@@ -1427,9 +1457,9 @@ int prgpu_render(prgpu_scene* s, uint32_t iter_begin, uint32_t iter_end)
 	if (iter_end == iter_begin)
 		return PRGPU_OK;
 	s->reduced.valid = false; // the reduced frame is stale from here on: downloads read the rank's own planes until the next reduce
-	if (s->ao_enabled) {
+	if (s->ao_enabled || s->vf_enabled) {
 		for (uint32_t it = iter_begin; it < iter_end; ++it) {
-			const int rc = render_ao_iteration(s, it);
+			const int rc = s->ao_enabled ? render_ao_iteration(s, it) : render_vf_iteration(s, it);
 			if (rc != PRGPU_OK)
 				return rc;
 			s->next_iteration = it + 1;
@@ -1527,7 +1557,7 @@ int prgpu_trace_counters_get(prgpu_scene* s, prgpu_trace_counters* out)
 	HIP_TRY(hipMemcpy(host, s->gstats, sizeof(host), hipMemcpyDeviceToHost));
 	out->rays_closest  = s->rays_closest;
 	out->rays_any	   = s->rays_any;
-	if (s->mode == prgpu_scene::PERSISTENT || s->ao_enabled) { // no per-launch host counts: every path ray is in the device statistics
+	if (s->mode == prgpu_scene::PERSISTENT || s->ao_enabled || s->vf_enabled) { // no per-launch host counts: every path ray is in the device statistics
 		out->rays_closest += host[PRGPU_STAT_PRIMARY_RAYS] + host[PRGPU_STAT_BOUNCE_RAYS];
 		out->rays_any += host[PRGPU_STAT_SHADOW_RAYS];
 	}
@@ -2088,6 +2118,8 @@ int prgpu_enable_lpe(prgpu_scene* s, uint32_t n, const char* const* expressions)
 		return PRGPU_OK;
 	if (s->ao_enabled) // (its one path, C<RD>E of LightPath::createCDL(1), is not built: refused, never a silently empty plane)
 		return fail(PRGPU_EUNSUPPORTED, "light path expressions are not provided with the ambient occlusion integrator");
+	if (s->vf_enabled) // (likewise: visualfeedback.cpp:110)
+		return fail(PRGPU_EUNSUPPORTED, "light path expressions are not provided with the visual feedback integrator");
 	HIP_TRY(hipSetDevice(s->device));
 	prd::DevLpe host;
 	std::memset(&host, 0, sizeof(host));
@@ -2154,6 +2186,8 @@ int prgpu_enable_ambient_occlusion(prgpu_scene* s, uint32_t sample_count)
 		return fail(PRGPU_EUNSUPPORTED, "light path expressions are not provided with the ambient occlusion integrator");
 	if (s->ao_enabled)
 		return fail(PRGPU_EINVAL, "ambient occlusion is already enabled");
+	if (s->vf_enabled)
+		return fail(PRGPU_EINVAL, "ambient occlusion cannot be enabled on a scene that renders with the visual feedback integrator");
 	HIP_TRY(hipSetDevice(s->device));
 	prd::AoState ao{};
 	ao.sample_count = sample_count;
@@ -2176,6 +2210,50 @@ int prgpu_enable_ambient_occlusion(prgpu_scene* s, uint32_t sample_count)
 	HIP_TRY(hipStreamSynchronize(s->stream)); // (the table's host copy goes out of scope)
 	s->ao		  = ao;
 	s->ao_enabled = true;
+	s->mode		  = prgpu_scene::LOCKSTEP; // iteration-synchronous, every pixel filter; the owned pixels go back to plain Morton order
+	const std::vector<prgpu_tile> tiles = s->tiles;
+	return apply_tiles(s, tiles.data(), (uint32_t)tiles.size());
+}
+
+int prgpu_visual_feedback_color(uint32_t index, float rgb[3])
+{
+	if (!rgb || index >= prd::VF_COLOURS)
+		return fail(PRGPU_EINVAL, "prgpu_visual_feedback_color: null argument or no such colour");
+	for (int c = 0; c < 3; ++c)
+		rgb[c] = PR_VF_COLOR_RGB[index][c];
+	return PRGPU_OK;
+}
+
+int prgpu_enable_visual_feedback(prgpu_scene* s, uint32_t mode, int weighting)
+{
+	if (!s)
+		return fail(PRGPU_EINVAL, "null scene");
+	if (s->next_iteration != 0)
+		return fail(PRGPU_EINVAL, "visual feedback must be enabled before the first iteration");
+	if (mode >= PRGPU_VF_MODE_COUNT)
+		return fail(PRGPU_EINVAL, "visual feedback: unknown mode " + std::to_string(mode));
+	if (s->ao_enabled)
+		return fail(PRGPU_EINVAL, "visual feedback cannot be enabled on a scene that renders with the ambient occlusion integrator");
+	if (s->ps.lpe)
+		return fail(PRGPU_EINVAL, "visual feedback cannot be enabled on a scene with light path expressions: they are not provided with it");
+	if (s->vf_enabled)
+		return fail(PRGPU_EINVAL, "visual feedback is already enabled");
+	HIP_TRY(hipSetDevice(s->device));
+	std::vector<float4> rows(prd::VF_COLOURS); // VFParametricCache (visualfeedback.cpp:314-324): every colour prepared once by the default upsampler
+	for (uint32_t c = 0; c < prd::VF_COLOURS; ++c) {
+		float k[3];
+		prgpu_host::rgb_to_coeffs(PR_VF_COLOR_RGB[c], k);
+		rows[c] = make_float4(k[0], k[1], k[2], 0.0f);
+	}
+	prd::VfState vf{};
+	vf.mode		 = mode;
+	vf.weighting = weighting ? 1u : 0u;
+	const int rc = s->upload(vf.colours, rows);
+	if (rc != PRGPU_OK)
+		return rc;
+	HIP_TRY(hipStreamSynchronize(s->stream)); // (the table's host copy goes out of scope)
+	s->vf		  = vf;
+	s->vf_enabled = true;
 	s->mode		  = prgpu_scene::LOCKSTEP; // iteration-synchronous, every pixel filter; the owned pixels go back to plain Morton order
 	const std::vector<prgpu_tile> tiles = s->tiles;
 	return apply_tiles(s, tiles.data(), (uint32_t)tiles.size());

@@ -42,12 +42,22 @@ class SceneBuilder:
         self._any_normals = False
         self._uv, self._any_uvs = [], False
         self.integrator, self.ao_sample_count = abi.INTEGRATOR_DIRECT, 0
+        self.vf_mode, self.vf_weighting = None, True
         self.set_camera(IDENTITY)
 
     def ambient_occlusion(self, sample_count=10):
         """(integrator :type 'ao' :sample_count N), ambientocclusion.cpp:107: a RenderContext of the built scene renders with it"""
         assert int(sample_count) >= 1, "sample_count must be at least 1"
         self.integrator, self.ao_sample_count = abi.INTEGRATOR_AO, int(sample_count)
+
+    def visual_feedback(self, mode, weighting=True):
+        """(integrator :type 'vf' :mode ... :weighting ...), visualfeedback.cpp:331: a RenderContext of the built scene renders with it;
+        `mode` is a PRGPU_VF_* number or its name (abi.VF_MODE_NAMES)"""
+        if isinstance(mode, str):
+            mode = abi.VF_MODES[mode.lower()]
+        assert 0 <= int(mode) < len(abi.VF_MODE_NAMES), "unknown visual feedback mode"
+        self.integrator, self.ao_sample_count = abi.INTEGRATOR_VF, 0
+        self.vf_mode, self.vf_weighting = int(mode), bool(weighting)
 
     # ---- spectral nodes -------------------------------------------------------------------------
     def _add_spec(self, **kw):
@@ -430,6 +440,7 @@ class SceneData:
         d.lights = self.lights
         self.desc = d
         self.integrator, self.ao_sample_count = b.integrator, b.ao_sample_count
+        self.vf_mode, self.vf_weighting = b.vf_mode, b.vf_weighting
 
     @property
     def settings(self):
@@ -475,7 +486,12 @@ class PrcScene:
         self.warnings = [w for w in lib.prgpu_prc_warnings(h).decode().split("\n") if w]
         kind, count = C.c_uint32(), C.c_uint32()
         abi.check(lib.prgpu_prc_integrator(h, C.byref(kind), C.byref(count)))
-        self.integrator, self.ao_sample_count = kind.value, count.value   # INTEGRATOR_DIRECT / INTEGRATOR_AO (:sample_count)
+        self.integrator, self.ao_sample_count = kind.value, count.value   # INTEGRATOR_DIRECT / INTEGRATOR_AO (:sample_count) / INTEGRATOR_VF
+        self.vf_mode, self.vf_weighting = None, True
+        if kind.value == abi.INTEGRATOR_VF:
+            mode, weighting = C.c_uint32(), C.c_int()
+            abi.check(lib.prgpu_prc_visual_feedback(h, C.byref(mode), C.byref(weighting)))
+            self.vf_mode, self.vf_weighting = mode.value, bool(weighting.value)   # :mode (PRGPU_VF_*), :weighting
 
     def sky_params(self):
         """{light index: (sun elevation, sun azimuth, turbidity, albedo[11])} of the scene's sky lights (what their SkyModel was built from)."""
