@@ -49,7 +49,7 @@ extern "C" {
 #endif
 
 #define PRGPU_API_VERSION 8 /* layout version of the structs below (prgpu_scene_desc::api_version); entry points added since keep it: round 5 added
-                               prgpu_pipeline_info_get, prgpu_comm_query, prgpu_reduced_planes */
+                               prgpu_pipeline_info_get, prgpu_comm_query, prgpu_reduced_planes; PRGPU_ENTITY_DISK is a new enumerator, no field moved */
 #define PRGPU_INVALID_ID 0xFFFFFFFFu /* PR_INVALID_ID, src/base/config/Constants.inl:6 */
 
 enum {
@@ -153,15 +153,23 @@ typedef struct prgpu_emission {
  * Described as ONE placeholder triangle whose three indices name the same vertex (never hit); primitive id 0;
  * N = normalMatrix * normalize(gradient(invTransform * P)), Tangent::frame, uv = 0 (quadric.cpp:95-108).  The occlusion callback of
  * the reference tests the UNBOUNDED surface from the box's entry on (no clip to the box's exit or the ray's extent): kept.
- * Emissive quadrics are rejected (the reference's sampleParameterPoint is a stub with pdf 0).  Every pipeline and the ray service trace them. */
-enum { PRGPU_ENTITY_MESH = 0, PRGPU_ENTITY_PLANE = 1, PRGPU_ENTITY_SPHERE = 2, PRGPU_ENTITY_QUADRIC = 3 };
+ * Emissive quadrics are rejected (the reference's sampleParameterPoint is a stub with pdf 0).  Every pipeline and the ray service trace them.
+ * DISK (src/plugins/main/entities/disk.cpp; geometry/Disk.h): an Embree RTC_GEOMETRY_TYPE_ORIENTED_DISC_POINT at M * (0,0,0) with the
+ * normal normalMatrix * (0,0,1) (not normalised) and the LOCAL `radius` -- the transform moves and turns the disk but does not scale what
+ * rays hit (disk.cpp:59-79, "Not affected by the transform?"): kept.  Both faces are hit, u = v = 0.  Described like the sphere: ONE
+ * placeholder triangle (its three indices are ignored), `radius` > PR_EPSILON (Disk::isValid, Disk.h:28-31); primitive id 0;
+ * N = normalize(normalMatrix * (0,0,1)), Tangent::frame, uv = 0 (disk.cpp:89-102).  May carry an `emission`: area = |det M| * pi radius^2
+ * (disk.cpp:36-42, IEntity.h:70), light points M * (r v cos 2 pi u, r v sin 2 pi u, 0) with the area pdf 1 / area (disk.cpp:81-87,
+ * Disk.h:19-26) -- the radius is linear in v, so the points are denser towards the centre than the pdf says, and under a scale they cover
+ * a larger disc than rays hit: both kept.  Every pipeline and the ray service trace disks. */
+enum { PRGPU_ENTITY_MESH = 0, PRGPU_ENTITY_PLANE = 1, PRGPU_ENTITY_SPHERE = 2, PRGPU_ENTITY_QUADRIC = 3, PRGPU_ENTITY_DISK = 4 };
 typedef struct prgpu_entity {
 	uint32_t first_tri;
 	uint32_t n_tris;
 	uint32_t emission;     /* emission index or PRGPU_INVALID_ID */
 	uint32_t has_normals;  /* MESH: 1: interpolate vertex normals (MeshEntity<*,true>), 0: geometric */
 	uint32_t kind;         /* PRGPU_ENTITY_* */
-	float    radius;       /* SPHERE: local radius (`:radius`, default 1) */
+	float    radius;       /* SPHERE, DISK: local radius (`:radius`, default 1) */
 	uint32_t has_uvs;      /* MESH: 1: the mesh has texture coordinates (MeshEntity<HasUV>, mesh.cpp:205-228): interpolated uv, and with
 	                          has_normals the tangent frame of Face::tangentFromUV (geometry/Face.h:80-98) */
 	uint32_t params;       /* QUADRIC: offset of its 16 floats in spectral_tables (0 otherwise) */
@@ -529,7 +537,7 @@ int prgpu_download_ao_samples(prgpu_scene* s, uint64_t* rng_state, float* org, f
  *                          an absent id is PRGPU_INVALID_ID, and 0xFFFFFFFF % 23 = 11
  *   COLORED_DISPLACE_ID    colour 11 on every hit: no entity ever sets GeometryPoint::DisplaceID (GeometryPoint.h:24)
  *   RAY_DIRECTION          red * a + green * b + blue * c, (a, b, c) = 0.5 * (direction + 1)
- *   PARAMETER              red * u + green * v + blue * t: the intersector's hit parameters (u = v = 0 on spheres and quadrics)
+ *   PARAMETER              red * u + green * v + blue * t: the intersector's hit parameters (u = v = 0 on spheres, quadrics and disks)
  *   INSIDE                 green for a back face (!signbit(NdotV)), red for a front face
  *   NDOTV                  green * -NdotV for NdotV < 0, else red * NdotV; NEVER weighted
  * and every mode but NDOTV multiplied by weight when `weighting` is non-zero.  The reference's colored_ray_id (a position in its ray

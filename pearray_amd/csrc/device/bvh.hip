@@ -48,6 +48,16 @@ __global__ void k_world_tris(uint32_t n, const float* __restrict__ positions, co
 			const float rr = E.sphere_r * 1.000002f + 1e-7f;
 			p			   = k == 0 ? c - v3(rr, rr, rr) : (k == 1 ? c + v3(rr, rr, rr) : c);
 			w			   = k == 0 ? 1.0f : (k == 2 ? E.sphere_r : 0.0f);
+		} else if (E.kind == PRGPU_ENTITY_DISK) { // placeholder triangle of an analytic disk, laid out like the sphere's; w of the first vertex is 2.
+			// The disc |x - c| <= r in the plane with unit normal n reaches r sqrt(1 - n_i^2) along axis i -- taken as r sqrt(n_j^2 + n_k^2),
+			// which does not cancel for a nearly axis-parallel disk (1 - n_i^2 loses a tilt below 3.5e-4) -- inflated like the sphere's
+			// radius, the absolute term being the floor that keeps a box around an axis-parallel disk (pad_box widens it further).
+			const V3 c	= v3(E.m[3], E.m[7], E.m[11]);
+			const V3 nn = normalized(mat3_mul(E.nm, v3(0.0f, 0.0f, 1.0f)));
+			const V3 h	= v3(E.sphere_r * sqrtf(nn.y * nn.y + nn.z * nn.z) * 1.000002f + 1e-7f, E.sphere_r * sqrtf(nn.x * nn.x + nn.z * nn.z) * 1.000002f + 1e-7f,
+							 E.sphere_r * sqrtf(nn.x * nn.x + nn.y * nn.y) * 1.000002f + 1e-7f);
+			p			   = k == 0 ? c - h : (k == 1 ? c + h : c);
+			w			   = k == 0 ? 2.0f : (k == 2 ? E.sphere_r : 0.0f);
 		}
 		wv[3 * t + k] = make_float4(p.x, p.y, p.z, w);
 		lo[0] = fminf(lo[0], p.x); lo[1] = fminf(lo[1], p.y); lo[2] = fminf(lo[2], p.z);
@@ -607,7 +617,7 @@ __global__ void k_validate(uint32_t n_inner, const uint32_t* __restrict__ inner_
 // leaf record: triangle k occupies floats [10k, 10k+10): v0, v1, v2, original triangle index; float 30 = count, float 31 = material classes
 __global__ void k_emit_leaves(uint32_t n, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri, const uint32_t* __restrict__ leaf_flag,
 							  const uint32_t* __restrict__ leaf_count, const uint32_t* __restrict__ leaf_idx, const uint32_t* __restrict__ leaf_unit, Rec64* __restrict__ recs,
-							  const uint8_t* __restrict__ tri_class)
+							  const uint8_t* __restrict__ tri_class, const uint32_t* __restrict__ tri_entity, const DevEntity* __restrict__ entities)
 {
 	const uint32_t pos = blockIdx.x * blockDim.x + threadIdx.x;
 	if (pos >= n || !leaf_flag[pos])
@@ -620,13 +630,20 @@ __global__ void k_emit_leaves(uint32_t n, const float4* __restrict__ wv, const u
 	for (uint32_t k = 0; k < cnt; ++k) {
 		const uint32_t t = sorted_tri[pos + k];
 		classes |= (tri_class ? (uint32_t)tri_class[t] : 0u) << (8u * k);
-		if (wv[3 * t].w != 0.0f) { // analytic sphere: centre, radius
-			const float4 c = wv[3 * t + 2];
-			f[10 * k]	   = c.x;
-			f[10 * k + 1]  = c.y;
-			f[10 * k + 2]  = c.z;
-			f[10 * k + 3]  = c.w;
-			f[10 * k + 9]  = __uint_as_float(t | PRIM_SPHERE_BIT);
+		if (wv[3 * t].w != 0.0f) { // analytic sphere: centre, radius; analytic disk (w = 2): centre, radius, the normal Embree is given (disk.cpp:62)
+			const float4 c	= wv[3 * t + 2];
+			const bool disk = wv[3 * t].w == 2.0f;
+			f[10 * k]		= c.x;
+			f[10 * k + 1]	= c.y;
+			f[10 * k + 2]	= c.z;
+			f[10 * k + 3]	= c.w;
+			if (disk) {
+				const V3 nrm  = mat3_mul(entities[tri_entity[t]].nm, v3(0.0f, 0.0f, 1.0f));
+				f[10 * k + 4] = nrm.x;
+				f[10 * k + 5] = nrm.y;
+				f[10 * k + 6] = nrm.z;
+			}
+			f[10 * k + 9] = __uint_as_float(t | (disk ? PRIM_DISK_BIT : PRIM_SPHERE_BIT));
 			continue;
 		}
 		for (int v = 0; v < 3; ++v) {
@@ -646,7 +663,7 @@ __global__ void k_emit_leaves(uint32_t n, const float4* __restrict__ wv, const u
 
 // tiny scenes (n <= 3): one inner record whose only child is the single leaf
 __global__ void k_tiny_scene(uint32_t n, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri, Rec64* __restrict__ recs, uint32_t* __restrict__ leaf_unit,
-							 const uint8_t* __restrict__ tri_class)
+							 const uint8_t* __restrict__ tri_class, const uint32_t* __restrict__ tri_entity, const DevEntity* __restrict__ entities)
 {
 	if (blockIdx.x != 0 || threadIdx.x != 0)
 		return;
@@ -664,13 +681,20 @@ __global__ void k_tiny_scene(uint32_t n, const float4* __restrict__ wv, const ui
 			lo[k] = fminf(lo[k], a[k]);
 			hi[k] = fmaxf(hi[k], b[k]);
 		}
-		if (wv[3 * t].w != 0.0f) { // analytic sphere: centre, radius
+		if (wv[3 * t].w != 0.0f) { // analytic sphere: centre, radius; analytic disk (w = 2): centre, radius, normal (as k_emit_leaves)
 			const float4 c	 = wv[3 * t + 2];
+			const bool disk	 = wv[3 * t].w == 2.0f;
 			leaf[10 * i]	 = c.x;
 			leaf[10 * i + 1] = c.y;
 			leaf[10 * i + 2] = c.z;
 			leaf[10 * i + 3] = c.w;
-			leaf[10 * i + 9] = __uint_as_float(t | PRIM_SPHERE_BIT);
+			if (disk) {
+				const V3 nrm	 = mat3_mul(entities[tri_entity[t]].nm, v3(0.0f, 0.0f, 1.0f));
+				leaf[10 * i + 4] = nrm.x;
+				leaf[10 * i + 5] = nrm.y;
+				leaf[10 * i + 6] = nrm.z;
+			}
+			leaf[10 * i + 9] = __uint_as_float(t | (disk ? PRIM_DISK_BIT : PRIM_SPHERE_BIT));
 			continue;
 		}
 		for (int v = 0; v < 3; ++v) {
@@ -1062,7 +1086,7 @@ bool build_lbvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream
 			HIPC(hipMalloc(&out.recs, sizeof(Rec64) * 4));
 			HIPC(hipMemsetAsync(out.recs, 0, sizeof(Rec64) * 4, stream));
 			HIPC(hipMalloc(&out.leaf_units, sizeof(uint32_t)));
-			hipLaunchKernelGGL(k_tiny_scene, dim3(1), dim3(64), 0, stream, n, wv, vals_sorted, out.recs, out.leaf_units, in.tri_class);
+			hipLaunchKernelGGL(k_tiny_scene, dim3(1), dim3(64), 0, stream, n, wv, vals_sorted, out.recs, out.leaf_units, in.tri_class, in.tri_entity, in.entities);
 			out.n_inner = 1;
 			out.n_leaf	= 1;
 			out.n_units = 4;
@@ -1120,7 +1144,7 @@ bool build_lbvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream
 							   inner_unit, out.leaf_units);
 			hipLaunchKernelGGL(k_emit_inner, dim3(G), dim3(B), 0, stream, (int)n, width, wv, vals_sorted, left, right, rf, rl, boxes, inner_flag, inner_idx, leaf_idx, gbase,
 							   inner_unit, out.recs);
-			hipLaunchKernelGGL(k_emit_leaves, dim3(G), dim3(B), 0, stream, n, wv, vals_sorted, leaf_flag, leaf_cnt, leaf_idx, out.leaf_units, out.recs, in.tri_class);
+			hipLaunchKernelGGL(k_emit_leaves, dim3(G), dim3(B), 0, stream, n, wv, vals_sorted, leaf_flag, leaf_cnt, leaf_idx, out.leaf_units, out.recs, in.tri_class, in.tri_entity, in.entities);
 			HIPC(hipGetLastError());
 			{ // gsize is free again: its first word takes the count of bad records
 				uint32_t bad = 0;

@@ -290,7 +290,7 @@ __device__ __forceinline__ void path_wave(const DevScene& sc, const PathState& p
 						cl_c += s.any ? 0 : 1;
 						cl_a += s.any ? 1 : 0;
 					}
-					trav_leaf_rec<MODE_MIXED, (FEATS & FEAT_SPHERES) != 0, (NQ > 1)>(s, st, q0, q1, q2, q3, q4, q5, q6, q7, top);
+					trav_leaf_rec<MODE_MIXED, (FEATS & ANA_ALL), (NQ > 1)>(s, st, q0, q1, q2, q3, q4, q5, q6, q7, top);
 				}
 			}
 			// a finished ray reports at once: the hit goes to LDS, the slot's pending word counts the ray down, and the ray that

@@ -85,14 +85,14 @@ struct DevEntity {
 	uint32_t first_tri, n_tris, emission, has_normals;
 	float vol_scale, world_area;
 	uint32_t light_id, kind; // kind: PRGPU_ENTITY_*
-	float sphere_r;			 // SPHERE: world radius (sphere.cpp:77-92); the centre is the translation (m[3], m[7], m[11])
+	float sphere_r;			 // SPHERE: world radius (sphere.cpp:77-92); the centre is the translation (m[3], m[7], m[11]); DISK: the LOCAL radius (disk.cpp:70)
 	uint32_t has_uvs;		 // MESH: texture coordinates present (interpolated uv, UV-derived tangent frame); QUADRIC: index into DevScene::quadrics
 							 // (no field of its own: the record's size and the argument block's layout feed the register allocation of every variant --
 							 // one more word here cost the C5 kernel 29 more spilled registers and 2 %)
 };
 
 constexpr uint32_t FEAT_DELTA_MATERIALS = 1u, FEAT_INFINITE_LIGHTS = 2u, FEAT_PLANES = 4u, FEAT_SPHERES = 8u, FEAT_AOVS = 16u, FEAT_SHAPE_LIGHTS = 32u, FEAT_TEXTURES = 64u,
-				   FEAT_ROUGH_MATERIALS = 128u, FEAT_LPE = 256u, FEAT_QUADRICS = 512u, FEAT_ALL = 1023u;
+				   FEAT_ROUGH_MATERIALS = 128u, FEAT_LPE = 256u, FEAT_QUADRICS = 512u, FEAT_DISKS = 1024u, FEAT_ALL = 2047u;
 
 // QuadricEntity (src/plugins/main/entities/quadric.cpp; `quadric`, `cone`, `cylinder`): an implicit surface inside a local box.  Embree
 // sees a user geometry: one primitive with the world box as bounds and the entity's own intersect / occluded callbacks.  Here the few
@@ -106,14 +106,14 @@ struct DevQuadric {
 	uint32_t entity;
 };
 
-// Area-light data of an analytic entity (one per entity, meaningful for emissive planes and spheres):
-// PlaneEntity::cache (plane.cpp:227-243) and SphereEntity (sphere.cpp:23-31,106-118)
+// Area-light data of an analytic entity (one per entity, meaningful for emissive planes, spheres and disks):
+// PlaneEntity::cache (plane.cpp:227-243), SphereEntity (sphere.cpp:23-31,106-118) and DiskEntity (disk.cpp:26,81-87)
 struct DevShapeLight {
 	float S[3], Ex[3], Ey[3], Ez[3], nrm[3]; // plane: world corner, unit axes, unit normal, normalMatrix * plane.normal() (not normalised)
 	float width, height;
 	float inv[12];	 // sphere: invTransform (3 rows of 4)
-	float pdf_cache; // sphere: 1 / worldSurfaceArea
-	float radius;	 // sphere: local radius
+	float pdf_cache; // sphere, disk: 1 / worldSurfaceArea
+	float radius;	 // sphere, disk: local radius
 	float pad[2];
 };
 // One record per AREA light (light id order) with everything next event estimation needs about a mesh light, so that sampling a
@@ -137,6 +137,8 @@ struct __attribute__((aligned(128))) DevMaterial {
 static_assert(sizeof(DevMaterial) == 128, "DevMaterial must be one 128-byte line");
 constexpr uint32_t LIGHT_TRI_FLOATS = 20; // per light triangle: local positions p0 p1 p2 (9), vertex normals n0 n1 n2 (9, zero without normals), 2 pad
 constexpr uint32_t PRIM_SPHERE_BIT = 0x40000000u; // leaf records: the primitive in this slot is an analytic sphere (centre, radius), not a triangle
+constexpr uint32_t PRIM_DISK_BIT   = 0x20000000u; // ... or an analytic disk (centre, radius, normal: floats 0..6 of the slot)
+constexpr uint32_t PRIM_INDEX_MASK = ~(PRIM_SPHERE_BIT | PRIM_DISK_BIT); // (a scene holds fewer than 2^29 triangles: setup.cpp, validate)
 
 // Infinite light (include/prgpu.h prgpu_light) with the matrices the kernels need
 struct DevInfLight {
@@ -865,6 +867,23 @@ __device__ __forceinline__ bool sphere_hit(const RayPre& r, V3 c, float radius, 
 	}
 	return false;
 }
+// Ray / oriented disc as Embree 3 publishes it (kernels/geometry/disc_intersector.h, the oriented overload) for the geometry of
+// disk.cpp:59-79: the plane through c with the normal n (NOT normalised: t is a quotient of two products with it), a hit in (tmin, limit]
+// whose point lies strictly inside the radius; both faces.  One division, taken only after den != 0: a ray in the disk's plane is a miss
+// and no 0 / 0 is compared.  (A tiny den may still give t = +-inf: o + t d is then inf or NaN and the rim test fails.)  Unpinned on ties:
+// a point exactly on the rim, t exactly at a window end.
+__device__ __forceinline__ bool disk_hit(const RayPre& r, V3 c, float radius, V3 n, float tmin, float limit, float& t)
+{
+	const float den = dot(r.d, n);
+	if (den == 0.0f)
+		return false;
+	const V3 c0 = c - r.o;
+	t			= dot(c0, n) / den;
+	if (!(t > tmin && t <= limit))
+		return false;
+	const V3 q = r.d * t - c0; // o + t d - c
+	return dot(q, q) < radius * radius;
+}
 // ---- quadric entities (quadric.cpp:131-248, geometry/Quadric.h, BoundingBox::intersectsRange) ---------------------------------------
 // std::min / std::max as the reference's libstdc++ evaluates them (NaN from 0 * inf on axis-parallel rays propagates the same way)
 __device__ __forceinline__ float std_min(float a, float b) { return b < a ? b : a; }
@@ -1422,6 +1441,15 @@ static __device__ __noinline__ void sphere_light_sample(const DevShapeLight& P, 
 		n = -n;
 	p	  = affine_mul(m, n * P.radius);
 	pdf_a = 2 * P.pdf_cache;
+}
+// DiskEntity::sampleParameterPoint(rnd) (disk.cpp:81-87, Disk::surfacePoint, Disk.h:19-26): the radius is LINEAR in v (not area-uniform,
+// as in the reference) while the pdf claims 1 / worldSurfaceArea; the point goes through the whole transform, scale included
+static __device__ __noinline__ void disk_light_sample(const DevShapeLight& P, const float* m, float r0, float r1, V3& p, float& pdf_a)
+{
+	float s, c;
+	pr_sincos_2pi(r0, s, c);
+	p	  = affine_mul(m, v3(P.radius * r1 * c, P.radius * r1 * s, 0.0f));
+	pdf_a = P.pdf_cache;
 }
 
 // same acceptance rule for a box entry distance that was computed earlier (stack entries, re-checks)

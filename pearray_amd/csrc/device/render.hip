@@ -273,8 +273,10 @@ __device__ __forceinline__ void trav_inner(const DevScene& sc, Trav& s, Stack& s
 }
 
 // Leaf step: fetch the leaf record (<= 3 triangles) and run the watertight test on each.
-// SPH: the leaf may hold analytic spheres (scenes with sphere entities); compiled out of the lean persistent kernel
-template <int M, bool SPH, bool CLS = false>
+// ANA: FEAT_SPHERES and / or FEAT_DISKS -- the leaf may hold analytic spheres / disks (scenes with such entities); compiled out of the
+// persistent kernel's variants that do not carry the feature
+constexpr uint32_t ANA_ALL = FEAT_SPHERES | FEAT_DISKS;
+template <int M, uint32_t ANA, bool CLS = false>
 __device__ __forceinline__ void leaf_test(Trav& s, const float4& q0, const float4& q1, const float4& q2, const float4& q3, const float4& q4, const float4& q5,
 										  const float4& q6, const float4& q7)
 {
@@ -288,16 +290,19 @@ __device__ __forceinline__ void leaf_test(Trav& s, const float4& q0, const float
 			float t, u, v;
 			const uint32_t prim = __float_as_uint(f[10 * k + 9]);
 			bool hit;
-			if (SPH && (prim & PRIM_SPHERE_BIT)) { // analytic sphere: centre in floats 0..2, radius in float 3 of the slot
+			if ((ANA & FEAT_SPHERES) && (prim & PRIM_SPHERE_BIT)) { // analytic sphere: centre in floats 0..2, radius in float 3 of the slot
 				u = v = 0.0f;
 				hit	  = sphere_hit(s.r, v3(f[10 * k], f[10 * k + 1], f[10 * k + 2]), f[10 * k + 3], s.tmin, s.best.t, t);
+			} else if ((ANA & FEAT_DISKS) && (prim & PRIM_DISK_BIT)) { // analytic disk: centre, radius, normal in floats 0..6 of the slot; u = v = 0 as Embree reports
+				u = v = 0.0f;
+				hit	  = disk_hit(s.r, v3(f[10 * k], f[10 * k + 1], f[10 * k + 2]), f[10 * k + 3], v3(f[10 * k + 4], f[10 * k + 5], f[10 * k + 6]), s.tmin, s.best.t, t);
 			} else {
 				hit = woop(s.r, v3(f[10 * k], f[10 * k + 1], f[10 * k + 2]), v3(f[10 * k + 3], f[10 * k + 4], f[10 * k + 5]),
 						   v3(f[10 * k + 6], f[10 * k + 7], f[10 * k + 8]), t, u, v)
 					  && t > s.tmin;
 			}
 			if (hit) {
-				const uint32_t tri = prim & ~PRIM_SPHERE_BIT;
+				const uint32_t tri = prim & ((ANA & FEAT_DISKS) ? PRIM_INDEX_MASK : ~PRIM_SPHERE_BIT);
 				if (ANY) {
 					if (t <= s.best.t)
 						s.best.tri = tri;
@@ -310,12 +315,12 @@ __device__ __forceinline__ void leaf_test(Trav& s, const float4& q0, const float
 		}
 	}
 }
-template <int M, bool SPH, bool CLS = false, typename STK>
+template <int M, uint32_t ANA, bool CLS = false, typename STK>
 __device__ __forceinline__ void trav_leaf_rec(Trav& s, STK& st, const float4& q0, const float4& q1, const float4& q2, const float4& q3, const float4& q4,
 											  const float4& q5, const float4& q6, const float4& q7, const uint2* top = nullptr)
 {
 	const bool ANY = M == MODE_ANY || (M == MODE_MIXED && s.any);
-	leaf_test<M, SPH, CLS>(s, q0, q1, q2, q3, q4, q5, q6, q7);
+	leaf_test<M, ANA, CLS>(s, q0, q1, q2, q3, q4, q5, q6, q7);
 	s.cur = REC_EMPTY;
 	if (ANY && s.best.tri != INVALID) { // occluded: done
 		st.reset();
@@ -329,7 +334,7 @@ __device__ __forceinline__ void trav_leaf(const DevScene& sc, Trav& s, Stack& st
 	const float4* __restrict__ rec = rec_ptr(sc.recs, s.cur);
 	const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4], q5 = rec[5], q6 = rec[6], q7 = rec[7];
 	const uint2 top = st.peek();
-	trav_leaf_rec<M, true>(s, st, q0, q1, q2, q3, q4, q5, q6, q7, &top);
+	trav_leaf_rec<M, ANA_ALL>(s, st, q0, q1, q2, q3, q4, q5, q6, q7, &top);
 }
 
 // The scene's quadric entities (Embree user geometries in the reference, entities/quadric.cpp:131-231), tested once per ray when a lane
@@ -552,6 +557,18 @@ __device__ __forceinline__ void geometry_point(const DevScene& sc, uint32_t tri,
 		g.material = sc.tri_material[tri];
 		g.emission = E.emission;
 		g.uv[0] = g.uv[1] = 0.0f; // Spherical::uv_from_normal is not built (validate rejects textured materials on spheres)
+		return;
+	}
+	if ((FEATS & FEAT_DISKS) && E.kind == PRGPU_ENTITY_DISK) { // DiskEntity::provideGeometryPoint (disk.cpp:89-102)
+		g.N = normalized(mat3_mul(E.nm, v3(0.0f, 0.0f, 1.0f)));
+		frame_duff(g.N, g.Nx, g.Ny);
+		g.Nx	   = normalized(g.Nx);
+		g.Ny	   = normalized(g.Ny);
+		g.entity   = e;
+		g.prim	   = 0;
+		g.material = sc.tri_material[tri];
+		g.emission = E.emission;
+		g.uv[0] = g.uv[1] = 0.0f; // pt.UV = query.UV: the (0, 0) of Embree's disc hit
 		return;
 	}
 	if ((FEATS & FEAT_QUADRICS) && E.kind == PRGPU_ENTITY_QUADRIC) { // QuadricEntity::provideGeometryPoint (quadric.cpp:95-108)
@@ -1790,7 +1807,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 				} else {
 					const uint32_t lid	 = sc.entities[gp.entity].light_id;
 					const float selProb	 = sc.light_cdf[lid + 1] - sc.light_cdf[lid];
-					float posPDF		 = 1.0f / sc.entities[gp.entity].world_area;
+					float posPDF		 = 1.0f / sc.entities[gp.entity].world_area; // (meshes; disks too: sampleParameterPointPDF() = mPDF_Cache = 1 / worldSurfaceArea, disk.cpp:26,87)
 					if ((FEATS & FEAT_SHAPE_LIGHTS) && sc.entities[gp.entity].kind == PRGPU_ENTITY_PLANE) { // seen from the previous vertex (plane.cpp:184-195)
 						const float4 lpos = ps.st[slot].last_pos;
 						posPDF			  = plane_light_pdf(sc.shape_lights[gp.entity], P, v3(lpos.x, lpos.y, lpos.z));
@@ -1925,6 +1942,9 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 					} else if ((FEATS & FEAT_SHAPE_LIGHTS) && LE.kind == PRGPU_ENTITY_SPHERE) { // sphere.cpp:106-116,128-134
 						sphere_light_sample(sc.shape_lights[le], LE.m, P, u0, u1, lp, pdf_a);
 						lgp.N = normalized_or_zero(lp - v3(LE.m[3], LE.m[7], LE.m[11]));
+					} else if ((FEATS & FEAT_DISKS) && LE.kind == PRGPU_ENTITY_DISK) { // disk.cpp:81-87; the normal of provideGeometryPoint (disk.cpp:94)
+						disk_light_sample(sc.shape_lights[le], LE.m, u0, u1, lp, pdf_a);
+						lgp.N = normalized(mat3_mul(LE.nm, v3(0.0f, 0.0f, 1.0f)));
 					} else {
 						float k0, k1;
 						const float f0		= modff(u0 * LE.n_tris, &k0);
@@ -2840,7 +2860,7 @@ __device__ __forceinline__ void path_persistent(const DevScene& sc, const PathSt
 						cl_c += s.any ? 0 : 1;
 						cl_a += s.any ? 1 : 0;
 					}
-					trav_leaf_rec<MODE_MIXED, (FEATS & FEAT_SPHERES) != 0, (NQ > 1)>(s, st, q0, q1, q2, q3, q4, q5, q6, q7, top);
+					trav_leaf_rec<MODE_MIXED, (FEATS & ANA_ALL), (NQ > 1)>(s, st, q0, q1, q2, q3, q4, q5, q6, q7, top);
 				}
 			}
 			if (COUNT) {
@@ -3130,7 +3150,7 @@ __global__ void k_tri_slot(DevScene sc, const uint32_t* __restrict__ leaf_units,
 	const float* f		= reinterpret_cast<const float*>(sc.recs + unit);
 	const uint32_t cnt	= __float_as_uint(f[30]);
 	for (uint32_t k = 0; k < cnt && k < 3u; ++k)
-		tri_slot[__float_as_uint(f[10 * k + 9]) & ~PRIM_SPHERE_BIT] = (unit << 2) | k;
+		tri_slot[__float_as_uint(f[10 * k + 9]) & PRIM_INDEX_MASK] = (unit << 2) | k;
 }
 template <bool WIDE>
 __global__ void __launch_bounds__(TRAV_BLOCK) k_service_closest_split(DevScene sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,

@@ -15,7 +15,7 @@
 //     (GeometryPoint.h:24, "TODO") and starts as PR_INVALID_ID, so colored_displace_id is colour 11 on every hit.
 //   * `ndotv` is never weighted (:188-197); every other mode is multiplied by |NdotV| when :weighting is on (:126-127 ...).
 //   * HitEntry::Parameter is (u, v, t) of the intersector (ShadingGroup.cpp:48-50): the triangle's barycentrics for a mesh, the quad's
-//     parameters for a plane (plane.cpp:214, as geometry_point restates them), and u = v = 0 for spheres and quadrics (quadric.cpp:169-170).
+//     parameters for a plane (plane.cpp:214, as geometry_point restates them), and u = v = 0 for spheres, quadrics (quadric.cpp:169-170) and disks.
 
 // SpectralUpsampler::compute (SpectralUpsampler.h:45-49) of colour row `c` at the sample's wavelengths.  The row index differs per lane
 // (id % 23): the rows live in a small device buffer, one 16-byte load per lane, never in an array indexed at run time.

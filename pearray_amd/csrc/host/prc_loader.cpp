@@ -17,6 +17,7 @@
 // types ...) is an error (PRGPU_EUNSUPPORTED) naming the block -- never silently dropped; blocks that do not influence the
 // radiance (outputs) are skipped with a warning.
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <fstream>
@@ -1291,7 +1292,7 @@ struct Loader {
 			add_plane(g, name);
 			return;
 		}
-		if (type == "sphere") { // sphere.cpp:157-168
+		if (type == "sphere" || type == "disk") { // sphere.cpp:157-168, disk.cpp:112-123: the same parameters
 			note_visibility_flags(g);
 			prgpu_entity e;
 			std::memset(&e, 0, sizeof(e));
@@ -1306,10 +1307,12 @@ struct Loader {
 				if (ev)
 					e.emission = it->second;
 			}
-			e.kind		= PRGPU_ENTITY_SPHERE;
+			e.kind		= type == "disk" ? PRGPU_ENTITY_DISK : PRGPU_ENTITY_SPHERE;
 			e.radius	= (float)get_number(g, "radius", 1.0);
-			if (!(e.radius > 0))
+			if (type == "sphere" && !(e.radius > 0))
 				fail(PRGPU_EINVAL, where(g) + ": sphere :radius must be positive");
+			if (type == "disk" && !(e.radius > FLT_EPSILON)) // Disk::isValid (Disk.h:28-31): nothing to hit, and the light sampler's pdf is 0 (disk.cpp:26)
+				fail(PRGPU_EINVAL, where(g) + ": disk :radius must be larger than 1.19e-7 (PR_EPSILON)");
 			transform_of(g, e.transform);
 			const Value* mv = g.get("material");
 			uint32_t mat	= PRGPU_INVALID_ID;
@@ -1396,7 +1399,7 @@ struct Loader {
 			return;
 		}
 		if (type != "mesh")
-			fail(PRGPU_EUNSUPPORTED, where(g) + ": entity type '" + type + "' is not supported (mesh, plane, sphere, quadric, cone and cylinder are; tessellate other primitives)");
+			fail(PRGPU_EUNSUPPORTED, where(g) + ": entity type '" + type + "' is not supported (mesh, plane, sphere, disk, quadric, cone and cylinder are; tessellate other primitives)");
 		note_visibility_flags(g);
 		const auto mit = meshes.find(get_string(g, "mesh", ""));
 		if (mit == meshes.end())

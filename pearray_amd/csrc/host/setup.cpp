@@ -376,6 +376,8 @@ void entity_tables(const prgpu_scene_desc* d, HostTables& t)
 			auto col_norm = [&](int j) { return std::sqrt((m[j] * m[j] + m[4 + j] * m[4 + j]) + m[8 + j] * m[8 + j]); };
 			E.sphere_r	  = src.radius * (((col_norm(0) + col_norm(1)) + col_norm(2)) / 3.0f);
 		}
+		if (src.kind == PRGPU_ENTITY_DISK) // disk.cpp:70: the LOCAL radius, "not affected by the transform"
+			E.sphere_r = src.radius;
 		float area	  = 0;
 		for (uint32_t tri = src.first_tri; tri < src.first_tri + src.n_tris; ++tri) {
 			t.tri_entity[tri] = e;
@@ -389,7 +391,7 @@ void entity_tables(const prgpu_scene_desc* d, HostTables& t)
 		E.world_area = E.vol_scale * area;
 	}
 	// analytic entities: their own surface areas and, when they emit, the data the light samplers need
-	// (PlaneEntity::cache, plane.cpp:227-243; SphereEntity, sphere.cpp:23-31,49-66)
+	// (PlaneEntity::cache, plane.cpp:227-243; SphereEntity, sphere.cpp:23-31,49-66; DiskEntity, disk.cpp:26,36-42)
 	bool any = false;
 	for (uint32_t e = 0; e < d->n_entities; ++e)
 		any = any || (d->entities[e].emission != PRGPU_INVALID_ID && d->entities[e].kind != PRGPU_ENTITY_MESH);
@@ -443,6 +445,10 @@ void entity_tables(const prgpu_scene_desc* d, HostTables& t)
 					L.inv[4 * r + c2] = E.nm[3 * c2 + r];
 				L.inv[4 * r + 3] = -((L.inv[4 * r] * m[3] + L.inv[4 * r + 1] * m[7]) + L.inv[4 * r + 2] * m[11]);
 			}
+		} else if (src.kind == PRGPU_ENTITY_DISK) { // worldSurfaceArea = volumeScalefactor * localSurfaceArea (IEntity.h:70; Disk.h:18: PR_PI r r)
+			E.world_area = E.vol_scale * ((3.14159265358979323846f * src.radius) * src.radius);
+			L.pdf_cache	 = src.radius > EPS_F ? 1.0f / E.world_area : 0.0f; // disk.cpp:26
+			L.radius	 = src.radius;
 		}
 	}
 	if (any)
@@ -576,11 +582,24 @@ void light_tables(const prgpu_scene_desc* d, HostTables& t)
 }
 
 // world-space vertex k of a triangle as the BVH builders see it: transformed mesh vertex, or for the placeholder triangle of an
-// analytic sphere the corners / centre of its (inflated) bounding box -- same values as k_world_tris and the checker
+// analytic sphere the corners / centre of its (inflated) bounding box -- same values as k_world_tris and the checker; for a disk the box of
+// k_world_tris restated (the same formula; the host's n / |n| may round differently from the device's, which only the scene radius and eps_t see)
 void world_vertex(const prgpu_scene_desc* d, const HostTables& t, uint32_t tri, int k, float w[3])
 {
 	const prd::DevEntity& E = t.entities[t.tri_entity[tri]];
 	const float* m			= E.m;
+	if (E.kind == PRGPU_ENTITY_DISK) {
+		const float n[3] = { E.nm[2], E.nm[5], E.nm[8] }; // normalMatrix * (0,0,1)
+		const float len	 = std::sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+		const float u[3] = { n[0] / len, n[1] / len, n[2] / len };
+		const float c[3] = { m[3], m[7], m[11] };
+		for (int r = 0; r < 3; ++r) {
+			const float a = u[(r + 1) % 3], b = u[(r + 2) % 3];
+			const float h = E.sphere_r * std::sqrt(a * a + b * b) * 1.000002f + 1e-7f;
+			w[r]		  = k == 0 ? c[r] - h : (k == 1 ? c[r] + h : c[r]);
+		}
+		return;
+	}
 	if (E.kind == PRGPU_ENTITY_SPHERE) {
 		const float rr = E.sphere_r * 1.000002f + 1e-7f;
 		const float c[3] = { m[3], m[7], m[11] };
@@ -1034,12 +1053,14 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 	}
 	if (expect != d->n_triangles)
 		return bad("entity triangle ranges do not cover the index buffer");
+	if (d->n_triangles >= prd::PRIM_DISK_BIT) // the leaf records flag analytic primitives in bits 29 and 30 of the triangle index (pr_device.h)
+		return bad("too many triangles (the limit is 2^29 - 1)", PRGPU_EUNSUPPORTED);
 	for (uint32_t t = 0; t < d->n_triangles; ++t)
 		if (d->tri_material[t] != PRGPU_INVALID_ID && d->tri_material[t] >= d->n_materials)
 			return bad("material index out of range");
 	for (uint32_t e = 0; e < d->n_entities; ++e) {
 		const prgpu_entity& E = d->entities[e];
-		if (E.kind > PRGPU_ENTITY_QUADRIC)
+		if (E.kind > PRGPU_ENTITY_DISK)
 			return bad("unknown entity kind");
 		if (E.kind == PRGPU_ENTITY_QUADRIC) {
 			if (E.n_tris != 1 || uint64_t(E.params) + 16u > d->n_spectral_table_values)
@@ -1058,6 +1079,8 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 		}
 		if (E.kind == PRGPU_ENTITY_SPHERE && (E.n_tris != 1 || !(E.radius > 0)))
 			return bad("a sphere entity is one placeholder triangle and a positive radius");
+		if (E.kind == PRGPU_ENTITY_DISK && (E.n_tris != 1 || !(E.radius > EPS_F) || !std::isfinite(E.radius)))
+			return bad("a disk entity is one placeholder triangle and a finite radius above 1.19e-7 (PR_EPSILON; Disk::isValid, Disk.h:28-31)");
 		if (E.kind == PRGPU_ENTITY_PLANE && E.n_tris != 2)
 			return bad("a plane entity is exactly two triangles (v0,v1,v3), (v2,v3,v1)");
 	}

@@ -563,8 +563,10 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 			sc.features |= prd::FEAT_PLANES;
 		else if (d->entities[e].kind == PRGPU_ENTITY_SPHERE)
 			sc.features |= prd::FEAT_SPHERES;
+		else if (d->entities[e].kind == PRGPU_ENTITY_DISK)
+			sc.features |= prd::FEAT_DISKS;
 	// measurement aid: run a scene with a larger kernel variant than it needs (same results; LPE and quadrics need data the scene does not have)
-	sc.features |= read_knobs().force_features & prd::FEAT_ALL & ~(prd::FEAT_LPE | prd::FEAT_QUADRICS);
+	sc.features |= read_knobs().force_features & prd::FEAT_ALL & ~(prd::FEAT_LPE | prd::FEAT_QUADRICS | prd::FEAT_DISKS);
 	sc.scene_radius	 = t.scene_radius;
 	sc.wl_cdf_size	 = (uint32_t)t.wl_cdf.size();
 	sc.wl_u_offset	 = t.wl_u_offset;
@@ -1672,7 +1674,7 @@ int prgpu_trace_closest(prgpu_scene* s, uint32_t n, const float* org, const floa
 	// closest-hit service rays take the split traversal (leaf tests through an LDS task queue: identical results, 17 % faster) unless
 	// PRGPU_TRACE_SPLIT=0 or the tree has too many records for the 24-bit task field
 	const bool split = read_knobs().trace_split;
-	if (split && s->sc.n_leaf > 0 && s->bvh_units < (1u << 24) && !(s->sc.features & (prd::FEAT_SPHERES | prd::FEAT_QUADRICS))) {
+	if (split && s->sc.n_leaf > 0 && s->bvh_units < (1u << 24) && !(s->sc.features & (prd::FEAT_SPHERES | prd::FEAT_QUADRICS | prd::FEAT_DISKS))) {
 		prd::launch_service_closest_split(s->sc, n, d_org, d_dir, d_tmin, d_tmax, d_e, d_p, d_u, d_v, d_t, s->ws, const_cast<uint32_t*>(s->sc.tri_slot), s->gstats, s->stream);
 	} else
 		prd::launch_service_closest(s->sc, n, d_org, d_dir, d_tmin, d_tmax, d_e, d_p, d_u, d_v, d_t, s->ws, s->gstats, s->stream);

@@ -338,6 +338,14 @@ class SceneBuilder:
         self.entities[e].radius = float(radius)
         return e
 
+    def add_disk(self, material, radius=1.0, transform=IDENTITY, emission=None):
+        """(entity :type 'disk' :radius r), disk.cpp:112-123: one placeholder triangle stands for the analytic primitive.  The transform
+        places and turns the disk; rays hit the LOCAL radius whatever its scale (disk.cpp:70), light samples follow the scale."""
+        e = self.add_mesh([[0, 0, 0], [0, 0, 0], [0, 0, 0]], [[0, 1, 2]], material, transform=transform, emission=emission)
+        self.entities[e].kind = abi.ENTITY_DISK
+        self.entities[e].radius = float(radius)
+        return e
+
     def add_quadric(self, material, parameters, box_min=(-1, -1, -1), box_max=(1, 1, 1), transform=IDENTITY):
         """(entity :type 'quadric' :parameters [A..J] :min :max), quadric.cpp:296-313: 3, 4 or 10 coefficients"""
         q = [float(v) for v in parameters]
