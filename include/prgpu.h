@@ -49,7 +49,8 @@ extern "C" {
 #endif
 
 #define PRGPU_API_VERSION 8 /* layout version of the structs below (prgpu_scene_desc::api_version); entry points added since keep it: round 5 added
-                               prgpu_pipeline_info_get, prgpu_comm_query, prgpu_reduced_planes; PRGPU_ENTITY_DISK is a new enumerator, no field moved */
+                               prgpu_pipeline_info_get, prgpu_comm_query, prgpu_reduced_planes; PRGPU_ENTITY_DISK and PRGPU_SPEC_IMAGE are new enumerators, no field moved;
+                               prgpu_image_load came with the latter */
 #define PRGPU_INVALID_ID 0xFFFFFFFFu /* PR_INVALID_ID, src/base/config/Constants.inl:6 */
 
 enum {
@@ -77,18 +78,28 @@ enum {
  *                      p[0] = su, p[1] = sv, p[2] = 0 (no scale) / 1 (isotropic: su for both) / 2 (anisotropic).  Allowed as a material
  *                      parameter (possibly nested in another CHECKER), not inside MUL and not as an emission; not on sphere entities
  *                      (their uv needs atan2/acos).
+ *   IMAGE              NonParametricImageNode of a `(texture :type color|grayscale|spectral ...)` block (src/loader/parser/TextureParser.cpp,
+ *                      src/loader/shader/ImageNode.cpp): lhs = width W, rhs = height H; table_offset (a multiple of 4) = first float of
+ *                      W*H + 1 texels of FOUR floats, (c0, c1, c2, 0) = prgpu_rgb_to_coeffs of the linear pixel, rows top-down; the last
+ *                      texel is that of RGB (0, 0, 0), the "black" texel; table_count = 4 (W*H + 1).  p[0] = interpolation (0 closest,
+ *                      1 bilinear), p[1] / p[2] = wrap in s / t (0 black, 1 clamp, 2 periodic, 3 mirror).  Looked up at s = u, t = 1 - v
+ *                      on OpenImageIO's texel grid: closest (int)floor(s W), bilinear around s W - 0.5; every index wrapped on its own
+ *                      (mirror: period 2W, second half reflected); a texel's spectrum is that of PARAMETRIC, and bilinear blends the four
+ *                      SPECTRA ((s00 (1-fx) + s10 fx)(1-fy) + (s01 (1-fx) + s11 fx) fy) -- the reference blends RGB, then upsamples.
+ *                      Placement as CHECKER: a material parameter or an operand of CHECKER; not inside MUL, not an emission, not on
+ *                      infinite lights, not on sphere entities.
  * MUL operands must have a smaller index than the node itself (topological order); so must CHECKER operands. */
 enum { PRGPU_SPEC_CONST = 0, PRGPU_SPEC_PARAMETRIC = 1, PRGPU_SPEC_PARAMETRIC_SCALED = 2,
-       PRGPU_SPEC_TABLE = 3, PRGPU_SPEC_MUL = 4, PRGPU_SPEC_SELLMEIER = 5, PRGPU_SPEC_CHECKER = 6 };
+       PRGPU_SPEC_TABLE = 3, PRGPU_SPEC_MUL = 4, PRGPU_SPEC_SELLMEIER = 5, PRGPU_SPEC_CHECKER = 6, PRGPU_SPEC_IMAGE = 7 };
 
 typedef struct prgpu_spectrum {
 	uint32_t kind;
 	float    p[4];          /* CONST: p[0]; PARAMETRIC*: a,b,c (, power) */
-	uint32_t table_offset;  /* TABLE: first sample in prgpu_scene_desc::spectral_tables */
-	uint32_t table_count;   /* TABLE: number of samples (>= 2) */
+	uint32_t table_offset;  /* TABLE: first sample in prgpu_scene_desc::spectral_tables; IMAGE: first float of the texels */
+	uint32_t table_count;   /* TABLE: number of samples (>= 2); IMAGE: 4 (W*H + 1) */
 	float    wl_start;      /* TABLE: wavelength of first sample [nm] */
 	float    wl_end;        /* TABLE: wavelength of last sample [nm] */
-	uint32_t lhs, rhs;      /* MUL: operand node indices; CHECKER: op1 (odd cells), op2 (even cells) */
+	uint32_t lhs, rhs;      /* MUL: operand node indices; CHECKER: op1 (odd cells), op2 (even cells); IMAGE: width, height */
 } prgpu_spectrum;
 
 /* LAMBERT     src/plugins/main/materials/lambert.cpp
@@ -354,6 +365,13 @@ int  prgpu_rgb_to_coeffs(const float rgb[3], float coeffs[3]);
  * `resolution` floats of scale, 3 * resolution^3 * 3 floats of coefficients (SpectralUpsampler.cpp:15-37; 64 is the reference's
  * resolution, 9.4 MB and 786 k fits -- about a minute on 8 threads).  prgpu_rgb_to_coeffs is `convert` (:78-146) on that table. */
 int  prgpu_write_rgb_coeff_table(const char* path, uint32_t resolution, int threads);
+/* Reads an image file as a `(texture ...)` block does: PNG (bit depth 8 or 16; grey, RGB, palette, grey + alpha, RGBA; not interlaced --
+ * PRGPU_EUNSUPPORTED) or PFM (`PF` / `Pf`, either byte order).  Grey is replicated to RGB, alpha and tRNS are dropped, integers are divided
+ * by 255 / 65535; PNG samples are then linearised as RGBConverter::linearize does (*linearised = 1), PFM is taken as linear (0).  Writes
+ * height x width x 3 floats, rows top-down, to `rgb`; rgb == NULL queries the size only.  A side above 4096 or an empty image is
+ * PRGPU_EINVAL, as is a damaged file (checksum, stream, filter); a missing or truncated one PRGPU_EIO.  channels_in_file and linearised
+ * may be NULL.  Host only. */
+int  prgpu_image_load(const char* path, uint32_t* width, uint32_t* height, uint32_t* channels_in_file, int* linearised, float* rgb);
 
 /* -- scene -------------------------------------------------------------------------------- */
 /* Validates + uploads the scene to HIP device `device`, builds the two-level LBVH on the device,

@@ -13,7 +13,7 @@ PRGPU_API_VERSION = 8
 INVALID_ID = 0xFFFFFFFF
 COMM_ID_BYTES = 128
 
-SPEC_CONST, SPEC_PARAMETRIC, SPEC_PARAMETRIC_SCALED, SPEC_TABLE, SPEC_MUL, SPEC_SELLMEIER, SPEC_CHECKER = range(7)
+SPEC_CONST, SPEC_PARAMETRIC, SPEC_PARAMETRIC_SCALED, SPEC_TABLE, SPEC_MUL, SPEC_SELLMEIER, SPEC_CHECKER, SPEC_IMAGE = range(8)
 MAT_LAMBERT, MAT_DIELECTRIC, MAT_CONDUCTOR, MAT_ROUGH_CONDUCTOR, MAT_ROUGH_DIELECTRIC, MAT_PRINCIPLED, MAT_MIRROR = 0, 1, 2, 3, 4, 5, 6
 MATF_ANISOTROPIC, MATF_NO_VNDF, MATF_HAS_TRANSMISSION = 1, 2, 4
 PRINCIPLED_PARAMS = ("diffuse_transmission", "specular_transmission", "specular_tint", "anisotropic", "flatness", "metallic", "sheen",
@@ -171,6 +171,7 @@ SYMBOLS = {
     "prgpu_settings_default": (None, [C.POINTER(Settings)]),
     "prgpu_rgb_to_coeffs": (C.c_int, [_F32P, _F32P]),
     "prgpu_write_rgb_coeff_table": (C.c_int, [C.c_char_p, C.c_uint32, C.c_int]),
+    "prgpu_image_load": (C.c_int, [C.c_char_p, _U32P, _U32P, _U32P, C.POINTER(C.c_int), _F32P]),
     "prgpu_scene_create": (C.c_int, [C.POINTER(SceneDesc), C.c_int, C.POINTER(_VP)]),
     "prgpu_scene_destroy": (None, [_VP]),
     "prgpu_set_tiles": (C.c_int, [_VP, C.POINTER(Tile), C.c_uint32]),

@@ -448,8 +448,62 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, uint32_t n_
 }
 
 // ---- shading helpers --------------------------------------------------------------------------------------
-__device__ __forceinline__ Blob spectrum_leaf(const DevScene& sc, const prgpu_spectrum& n, const Blob& wl)
+// One texel index of an image texture along an axis of `n` texels, wrapped by `mode` (0 black, 1 clamp, 2 periodic, 3 mirror: period 2n,
+// second half reflected); -1 selects the black texel.  OpenImageIO's wrap functions (texture.h, TextureOpt::Wrap), restated.
+__device__ __forceinline__ int image_wrap(int i, int n, int mode)
 {
+	if (mode == 1)
+		return min(max(i, 0), n - 1);
+	if (mode == 2) {
+		const int r = i % n;
+		return r < 0 ? r + n : r;
+	}
+	if (mode == 3) {
+		int r = i % (2 * n);
+		r	  = r < 0 ? r + 2 * n : r;
+		return r >= n ? 2 * n - 1 - r : r;
+	}
+	return (i < 0 || i >= n) ? -1 : i;
+}
+// a texel coordinate as an integer the wraps can take: floor, held inside +-2^30 (a NaN ends at the lower bound)
+__device__ __forceinline__ int image_floor(float x) { return (int)fminf(fmaxf(floorf(x), -1073741824.0f), 1073741824.0f); }
+__device__ __forceinline__ Blob image_texel_spectrum(const float4 c, const Blob& wl)
+{
+	const float p[3] = { c.x, c.y, c.z };
+	return blob4(upsample(p, wl.v[0]), upsample(p, wl.v[1]), upsample(p, wl.v[2]), upsample(p, wl.v[3]));
+}
+// PRGPU_SPEC_IMAGE (NonParametricImageNode::eval, shader/ImageNode.cpp, on OpenImageIO's texel grid): s = u, t = 1 - v; a texel is one
+// aligned 16-byte record (c0, c1, c2, 0), texel W H the black one.  Bilinear blends the four SPECTRA in a fixed order (the reference
+// blends RGB, then upsamples: DESIGN.md section 2.6); its four loads are issued before the first upsample.
+__device__ __forceinline__ Blob image_eval(const DevScene& sc, const prgpu_spectrum& n, const Blob& wl, const float uv[2])
+{
+	const int W = (int)n.lhs, H = (int)n.rhs, black = W * H;
+	const int ws = (int)n.p[1], wt = (int)n.p[2];
+	const float4* __restrict__ tex = reinterpret_cast<const float4*>(sc.tables + n.table_offset);
+	const float s = uv[0], t = 1.0f - uv[1];
+	if (n.p[0] == 0.0f) {
+		const int i = image_wrap(image_floor(s * W), W, ws), j = image_wrap(image_floor(t * H), H, wt);
+		return image_texel_spectrum(tex[(i < 0 || j < 0) ? black : j * W + i], wl);
+	}
+	const float x = s * W - 0.5f, y = t * H - 0.5f;
+	const float x0 = floorf(x), y0 = floorf(y);
+	const float fx = x - x0, fy = y - y0;
+	const int ia = image_floor(x), ja = image_floor(y);
+	const int i0 = image_wrap(ia, W, ws), i1 = image_wrap(ia + 1, W, ws), j0 = image_wrap(ja, H, wt), j1 = image_wrap(ja + 1, H, wt);
+	const float4 c00 = tex[(i0 < 0 || j0 < 0) ? black : j0 * W + i0], c10 = tex[(i1 < 0 || j0 < 0) ? black : j0 * W + i1];
+	const float4 c01 = tex[(i0 < 0 || j1 < 0) ? black : j1 * W + i0], c11 = tex[(i1 < 0 || j1 < 0) ? black : j1 * W + i1];
+	const Blob s00 = image_texel_spectrum(c00, wl), s10 = image_texel_spectrum(c10, wl), s01 = image_texel_spectrum(c01, wl), s11 = image_texel_spectrum(c11, wl);
+	Blob b;
+	for (int k = 0; k < 4; ++k)
+		b.v[k] = (s00.v[k] * (1.0f - fx) + s10.v[k] * fx) * (1.0f - fy) + (s01.v[k] * (1.0f - fx) + s11.v[k] * fx) * fy;
+	return b;
+}
+// IMG: the FEAT_IMAGES builds, whose material parameters may be image textures looked up at the shading point's `uv`
+template <bool IMG = false>
+__device__ __forceinline__ Blob spectrum_leaf(const DevScene& sc, const prgpu_spectrum& n, const Blob& wl, const float* uv = nullptr)
+{
+	if (IMG && n.kind == PRGPU_SPEC_IMAGE)
+		return image_eval(sc, n, wl, uv);
 	switch (n.kind) {
 	case PRGPU_SPEC_CONST: return blob(n.p[0]);
 	case PRGPU_SPEC_PARAMETRIC: return blob4(upsample(n.p, wl.v[0]), upsample(n.p, wl.v[1]), upsample(n.p, wl.v[2]), upsample(n.p, wl.v[3]));
@@ -482,12 +536,13 @@ __device__ __forceinline__ Blob spectrum_leaf(const DevScene& sc, const prgpu_sp
 	}
 }
 // FloatSpectralNode::eval for the flattened network (MUL operands are leaves; validated at scene creation)
-__device__ __forceinline__ Blob spectrum_eval(const DevScene& sc, uint32_t id, const Blob& wl)
+template <bool IMG = false>
+__device__ __forceinline__ Blob spectrum_eval(const DevScene& sc, uint32_t id, const Blob& wl, const float* uv = nullptr)
 {
 	const prgpu_spectrum& n = sc.spectra[id];
-	if (n.kind == PRGPU_SPEC_MUL)
+	if (n.kind == PRGPU_SPEC_MUL) // (no image inside a product: validated at scene creation)
 		return spectrum_leaf(sc, sc.spectra[n.lhs], wl) * spectrum_leaf(sc, sc.spectra[n.rhs], wl);
-	return spectrum_leaf(sc, n, wl);
+	return spectrum_leaf<IMG>(sc, n, wl, uv);
 }
 
 // the same for a node (and the operands of a product node) already in registers: DevLight / DevMaterial carry copies
@@ -498,13 +553,15 @@ __device__ __forceinline__ Blob spectrum_eval_copy(const DevScene& sc, const prg
 	return spectrum_leaf(sc, n, wl);
 }
 // albedo / specularity of a material: the copy next to the material unless a texture resolved the parameter to another node
-__device__ __forceinline__ Blob albedo_eval(const DevScene& sc, const prgpu_material& mat, const prgpu_spectrum& copy, uint32_t copy_id, const Blob& wl)
+template <bool IMG = false>
+__device__ __forceinline__ Blob albedo_eval(const DevScene& sc, const prgpu_material& mat, const prgpu_spectrum& copy, uint32_t copy_id, const Blob& wl, const float* uv = nullptr)
 {
 	if (mat.albedo != copy_id || copy.kind == PRGPU_SPEC_MUL)
-		return spectrum_eval(sc, mat.albedo, wl);
-	return spectrum_leaf(sc, copy, wl);
+		return spectrum_eval<IMG>(sc, mat.albedo, wl, uv);
+	return spectrum_leaf<IMG>(sc, copy, wl, uv);
 }
-// CheckerboardNode::eval (CheckerboardNode.cpp:26-48): a textured material parameter resolves to the plain node of the uv cell
+// CheckerboardNode::eval (CheckerboardNode.cpp:26-48): a textured material parameter resolves to the plain node of the uv cell -- which
+// may be an image texture (it passes through: the evaluation above looks it up)
 __device__ __forceinline__ uint32_t resolve_texture(const DevScene& sc, uint32_t id, const float uv[2])
 {
 	while (id != INVALID && sc.spectra[id].kind == PRGPU_SPEC_CHECKER) {
@@ -1084,8 +1141,6 @@ __global__ void __launch_bounds__(TRAV_BLOCK) k_trace_closest(DevScene sc, PathS
 // (DevScene::features == 0, e.g. the C4 benchmark scene): delta and rough materials, infinite lights, planes, spheres, textures and AOVs
 // are compiled out, which keeps their registers and spills out of the hot kernel; FEATS = FEAT_DELTA_MATERIALS adds the smooth dielectric /
 // conductor / mirror closures only (glass and metal scenes); FEAT_ALL is everything.
-// one shared out-of-line copy of the spectral node evaluation for the (cold, large) rough / principled closures
-static __device__ PR_CLOSURE Blob spectrum_eval_cold(const DevScene& sc, uint32_t id, const Blob& wl) { return spectrum_eval(sc, id, wl); }
 // ---- material evaluation for next event estimation: IMaterial::eval in tangent space ---------------------
 __device__ __forceinline__ RoughDistribution rough_distribution(const prgpu_material& m)
 {
@@ -1347,71 +1402,24 @@ static __device__ PR_CLOSURE void principled_eval_pdf(const Principled& c, V3 V,
 	pdf	   = c.pdf(V, L);
 }
 static __device__ PR_CLOSURE V3 principled_sample(const Principled& c, uint64_t& rnd, V3 V) { return c.sample(rnd, V); }
-__device__ __forceinline__ Principled principled_closure(const DevScene& s, const prgpu_material& m, const Blob& wl, const Blob& cie_y) // createClosure :475-497, ctor :63-84
-{
-	Principled p;
-	p.base = spectrum_eval_cold(s, m.albedo, wl);
-	p.ior  = spectrum_eval_cold(s, m.ior, wl);
-	p.cie_y = cie_y;
-	p.has_trans		  = (m.flags & PRGPU_MATF_HAS_TRANSMISSION) != 0;
-	p.thin			  = m.thin != 0;
-	p.vndf			  = (m.flags & PRGPU_MATF_NO_VNDF) == 0;
-	p.diff_trans	  = p.has_trans ? m.principled[PRGPU_PRINCIPLED_DIFFUSE_TRANSMISSION] : 0.0f;
-	p.spec_trans	  = p.has_trans ? m.principled[PRGPU_PRINCIPLED_SPECULAR_TRANSMISSION] : 0.0f;
-	p.roughness		  = m.roughness_x;
-	p.anisotropic	  = m.principled[PRGPU_PRINCIPLED_ANISOTROPIC];
-	p.spec_tint		  = m.principled[PRGPU_PRINCIPLED_SPECULAR_TINT];
-	p.flatness		  = m.principled[PRGPU_PRINCIPLED_FLATNESS];
-	p.metallic		  = m.principled[PRGPU_PRINCIPLED_METALLIC];
-	p.sheen			  = m.principled[PRGPU_PRINCIPLED_SHEEN];
-	p.sheen_tint	  = m.principled[PRGPU_PRINCIPLED_SHEEN_TINT];
-	p.clearcoat		  = m.principled[PRGPU_PRINCIPLED_CLEARCOAT];
-	p.clearcoat_gloss = m.principled[PRGPU_PRINCIPLED_CLEARCOAT_GLOSS];
-	return p;
-}
-// RoughConductorMaterial::eval (roughconductor.cpp:41-65), RoughDielectricMaterial::eval (roughdielectric.cpp:184-205).
-// `delta`: MaterialSampleFlag::DeltaDistribution.  Out of line: only scenes with rough materials pay for it.
-static __device__ PR_CLOSURE void rough_eval(const DevScene& s, const prgpu_material& mat, const Blob& wl, const Blob& cie_y, V3 Vt, V3 Lt, Blob& weight, Blob& pdf, bool& delta)
-{
-	if (mat.kind == PRGPU_MAT_PRINCIPLED) { // PrincipledMaterial::eval (principled.cpp:499-528)
-		const Principled c = principled_closure(s, mat, wl, cie_y);
-		delta			   = c.is_delta();
-		if (delta) {
-			weight = blob(0);
-			pdf	   = blob(0);
-			return;
-		}
-		principled_eval_pdf(c, Vt, Lt, weight, pdf);
-		return;
-	}
-	const RoughDistribution d = rough_distribution(mat);
-	delta					  = d.is_delta();
-	if (delta) {
-		weight = blob(0);
-		pdf	   = blob(0);
-		return;
-	}
-	if (mat.kind == PRGPU_MAT_ROUGH_CONDUCTOR) {
-		const Blob eta = spectrum_eval_cold(s, mat.ior, wl), kk = spectrum_eval_cold(s, mat.k, wl);
-		Blob factor;
-		for (int i = 0; i < 4; ++i)
-			factor.v[i] = mf_reflection_eval(d, Lt, Vt, true, eta.v[i], kk.v[i]);
-		weight = spectrum_eval_cold(s, mat.albedo, wl) * factor;
-		pdf	   = blob(mf_reflection_pdf(d, Lt, Vt));
-	} else {
-		const Blob spec	 = spectrum_eval_cold(s, mat.albedo, wl);
-		const Blob trans = mat.transmission != INVALID ? spectrum_eval_cold(s, mat.transmission, wl) : spec;
-		const Blob ior	 = spectrum_eval_cold(s, mat.ior, wl);
-		weight			 = rough_dielectric_eval(d, Vt, Lt, spec, trans, ior);
-		pdf				 = rough_dielectric_pdf(d, Vt, Lt, ior);
-	}
-}
+// spectrum_eval_cold (one shared out-of-line copy of the spectral node evaluation for the cold, large closures), principled_closure
+// (createClosure :475-497, ctor :63-84), rough_eval and rough_sample -- and their _uv forms for the FEAT_IMAGES variants
+#define PR_CLOSURES_IMG 0
+#include "rough_closures.inl"
+#undef PR_CLOSURES_IMG
+#define PR_CLOSURES_IMG 1
+#include "rough_closures.inl"
+#undef PR_CLOSURES_IMG
 // IMaterial::eval for next event estimation: LambertMaterial::eval (lambert.cpp:33-42) inline, the rough closures out of line
 template <uint32_t FEATS>
-__device__ __forceinline__ void material_eval(const DevScene& s, const prgpu_material& mat, const Blob& albedo, const Blob& wl, const Blob& cie_y, V3 Vt, V3 Lt, Blob& weight, Blob& pdf, bool& delta)
+__device__ __forceinline__ void material_eval(const DevScene& s, const prgpu_material& mat, const Blob& albedo, const Blob& wl, const Blob& cie_y, V3 Vt, V3 Lt, Blob& weight, Blob& pdf, bool& delta,
+											  const float* uv /* of the shading point: read by the FEAT_IMAGES builds only */)
 {
 	if ((FEATS & FEAT_ROUGH_MATERIALS) && (mat.kind == PRGPU_MAT_ROUGH_CONDUCTOR || mat.kind == PRGPU_MAT_ROUGH_DIELECTRIC || mat.kind == PRGPU_MAT_PRINCIPLED)) {
-		rough_eval(s, mat, wl, cie_y, Vt, Lt, weight, pdf, delta);
+		if (FEATS & FEAT_IMAGES)
+			rough_eval_uv(s, mat, wl, cie_y, Vt, Lt, weight, pdf, delta, uv);
+		else
+			rough_eval(s, mat, wl, cie_y, Vt, Lt, weight, pdf, delta);
 		return;
 	}
 	delta			= false;
@@ -1419,70 +1427,6 @@ __device__ __forceinline__ void material_eval(const DevScene& s, const prgpu_mat
 	const float dt	= same ? (mat.two_sided ? fabsf(Lt.z) : fmaxf(0.0f, Lt.z)) : 0.0f;
 	weight			= (albedo * dt) * PR_INV_PI_F;
 	pdf				= blob(dt * PR_INV_PI_F);
-}
-// RoughConductorMaterial::sample (roughconductor.cpp:83-117), RoughDielectricMaterial::sample (roughdielectric.cpp:222-254)
-static __device__ PR_CLOSURE void rough_sample(const DevScene& s, const prgpu_material& mat, const Blob& wl, const Blob& cie_y, V3 Vt, uint64_t& rnd, V3& Lt, Blob& integral_weight, Blob& pdf_s,
-										  bool& delta, bool& hero_collapsing)
-{
-	if (mat.kind == PRGPU_MAT_PRINCIPLED) { // PrincipledMaterial::sample (principled.cpp:548-590)
-		const Principled c = principled_closure(s, mat, wl, cie_y);
-		Lt				   = principled_sample(c, rnd, Vt);
-		delta			   = c.is_delta();
-		hero_collapsing	   = false; // the material sets no SpectralVarying flag
-		if (v3_is_zero(Lt, 1e-5f)) {
-			Lt				= v3(0, 0, 0);
-			integral_weight = blob(0);
-			pdf_s			= blob(0);
-			return;
-		}
-		principled_eval_pdf(c, Vt, Lt, integral_weight, pdf_s);
-		if (pdf_s.v[0] > PR_EPS)
-			integral_weight = integral_weight / pdf_s.v[0];
-		if (delta)
-			pdf_s = blob(1);
-		return;
-	}
-	const RoughDistribution d = rough_distribution(mat);
-	delta					  = d.is_delta();
-	if (mat.kind == PRGPU_MAT_ROUGH_CONDUCTOR) {
-		const float u0 = rng_float(rnd), u1 = rng_float(rnd);
-		Lt				= mf_reflection_sample(d, u0, u1, Vt);
-		hero_collapsing = delta && ((s.spectra[mat.ior].kind == PRGPU_SPEC_SELLMEIER) || (s.spectra[mat.k].kind == PRGPU_SPEC_SELLMEIER));
-		if (!sv_same_hemisphere(Vt, Lt)) { // MaterialSampleOutput::Reject
-			Lt				= v3(0, 0, 0);
-			integral_weight = blob(0);
-			pdf_s			= blob(0);
-			return;
-		}
-		const Blob eta = spectrum_eval_cold(s, mat.ior, wl), kk = spectrum_eval_cold(s, mat.k, wl);
-		Blob factor;
-		for (int i = 0; i < 4; ++i)
-			factor.v[i] = mf_reflection_eval(d, Lt, Vt, true, eta.v[i], kk.v[i]);
-		integral_weight = spectrum_eval_cold(s, mat.albedo, wl) * factor;
-		pdf_s			= blob(mf_reflection_pdf(d, Lt, Vt));
-	} else {
-		const Blob spec	 = spectrum_eval_cold(s, mat.albedo, wl);
-		const Blob trans = mat.transmission != INVALID ? spectrum_eval_cold(s, mat.transmission, wl) : spec;
-		const Blob ior	 = spectrum_eval_cold(s, mat.ior, wl);
-		hero_collapsing	 = delta && (s.spectra[mat.ior].kind == PRGPU_SPEC_SELLMEIER);
-		// RoughDielectricClosure::sample (roughdielectric.cpp:124-137): branch on the hero wavelength's Fresnel term
-		const float F  = fresnel_dielectric(Vt.z, DIELECTRIC_AIR, ior.v[0]);
-		const float ub = rng_float(rnd);
-		const float u0 = rng_float(rnd), u1 = rng_float(rnd);
-		Lt = ub <= F ? mf_reflection_sample(d, u0, u1, Vt) : mf_transmission_sample(d, u0, u1, Vt, DIELECTRIC_AIR, ior.v[0]);
-		if (v3_is_zero(Lt, 1e-5f)) { // Eigen isZero() with the default precision
-			Lt				= v3(0, 0, 0);
-			integral_weight = blob(0);
-			pdf_s			= blob(0);
-			return;
-		}
-		integral_weight = rough_dielectric_eval(d, Vt, Lt, spec, trans, ior);
-		pdf_s			= rough_dielectric_pdf(d, Vt, Lt, ior);
-	}
-	if (pdf_s.v[0] > PR_EPS)
-		integral_weight = integral_weight / pdf_s.v[0];
-	if (delta)
-		pdf_s = blob(1);
 }
 
 // CIESimpleSkyLight::radiance (cie_sky.cpp:108-126) for a world direction; (z + 1.01)^10 by squaring in fp32
@@ -1845,7 +1789,8 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 			const Blob cie_y_blob	 = blob4(cie.y[0], cie.y[1], cie.y[2], cie.y[3]);
 			// albedo / specularity at the path's wavelengths, once: IMaterial::eval and ::sample of a vertex evaluate the same node at
 			// the same wavelengths (lambert.cpp:38,66; mirror / conductor / dielectric sample).  The rough closures fetch their own.
-			const Blob albedo_v = roughMat ? blob(0) : albedo_eval(sc, mat, dmat.albedo, dmat.m.albedo, wl);
+			constexpr bool IMG	= (FEATS & FEAT_IMAGES) != 0u; // material parameters may be image textures: their evaluation takes the point's uv
+			const Blob albedo_v = roughMat ? blob(0) : albedo_eval<IMG>(sc, mat, dmat.albedo, dmat.m.albedo, wl, gp.uv);
 			if (cfg.nee && !deltaMat && !hasEmission && (sc.n_lights + ((FEATS & FEAT_INFINITE_LIGHTS) ? sc.n_inf_lights : 0u))) { // direct.cpp:100-101
 				// ---- handleNEE
 				do {
@@ -1878,7 +1823,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 						const V3 Lt = to_tangent_space(N, gp.Nx, gp.Ny, L);
 						Blob weight, bsdf_pdf;
 						bool evalDelta;
-						material_eval<FEATS>(sc, mat, albedo_v, wl, cie_y_blob, Vt, Lt, weight, bsdf_pdf, evalDelta);
+						material_eval<FEATS>(sc, mat, albedo_v, wl, cie_y_blob, Vt, Lt, weight, bsdf_pdf, evalDelta, gp.uv);
 						if (evalDelta) // direct.cpp:269-270
 							break;
 						const Blob bsdfWvlPdfS = bsdf_pdf * hf;
@@ -1988,7 +1933,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 					const V3 Lt = to_tangent_space(N, gp.Nx, gp.Ny, L);
 					Blob weight, bsdf_pdf;
 					bool evalDelta;
-					material_eval<FEATS>(sc, mat, albedo_v, wl, cie_y_blob, Vt, Lt, weight, bsdf_pdf, evalDelta);
+					material_eval<FEATS>(sc, mat, albedo_v, wl, cie_y_blob, Vt, Lt, weight, bsdf_pdf, evalDelta, gp.uv);
 					if (evalDelta) // direct.cpp:269-270
 						break;
 					const Blob bsdfWvlPdfS = bsdf_pdf * hf;
@@ -2049,7 +1994,9 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 				Blob integral_weight, pdf_s;
 				bool heroCollapsing = false;
 				bool sampleDelta	= deltaMat;
-				if (roughMat) {
+				if (roughMat && IMG) {
+					rough_sample_uv(sc, mat, wl, cie_y_blob, Vt, rnd, Lt, integral_weight, pdf_s, sampleDelta, heroCollapsing, gp.uv);
+				} else if (roughMat) {
 					rough_sample(sc, mat, wl, cie_y_blob, Vt, rnd, Lt, integral_weight, pdf_s, sampleDelta, heroCollapsing);
 				} else if ((FEATS & FEAT_DELTA_MATERIALS) && mat.kind == PRGPU_MAT_MIRROR) {
 					// MirrorMaterial::sample (mirror.cpp:51-60)
@@ -2059,7 +2006,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 				} else if ((FEATS & FEAT_DELTA_MATERIALS) && mat.kind == PRGPU_MAT_CONDUCTOR) {
 					// ConductorMaterial::sample (conductor.cpp:54-71): mirror, per-wavelength Fresnel term, no random number
 					pdf_s		   = blob(1);
-					const Blob eta = spectrum_eval(sc, mat.ior, wl), kk = spectrum_eval(sc, mat.k, wl);
+					const Blob eta = spectrum_eval<IMG>(sc, mat.ior, wl, gp.uv), kk = spectrum_eval<IMG>(sc, mat.k, wl, gp.uv);
 					Blob fresnel;
 					for (int i = 0; i < 4; ++i)
 						fresnel.v[i] = fresnel_conductor(fabsf(Vt.z), 1.0f, eta.v[i], kk.v[i]);
@@ -2069,7 +2016,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 				} else if (deltaMat) {
 					// DielectricMaterial::sample (dielectric.cpp:60-114), camera rays
 					pdf_s		  = blob(1);
-					const Blob n2 = spectrum_eval(sc, mat.ior, wl);
+					const Blob n2 = spectrum_eval<IMG>(sc, mat.ior, wl, gp.uv);
 					float F		  = fresnel_dielectric(Vt.z, DIELECTRIC_AIR, n2.v[0]);
 					if (mat.thin && F < 1.0f)
 						F += (1 - F) * F / (F + 1);
@@ -2078,7 +2025,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 						Lt				= v3(-Vt.x, -Vt.y, Vt.z);
 						integral_weight = rWeight;
 					} else {
-						const Blob tWeight = mat.transmission != INVALID ? spectrum_eval(sc, mat.transmission, wl) : rWeight;
+						const Blob tWeight = mat.transmission != INVALID ? spectrum_eval<IMG>(sc, mat.transmission, wl, gp.uv) : rWeight;
 						if (mat.thin) {
 							Lt				= -Vt;
 							integral_weight = tWeight;

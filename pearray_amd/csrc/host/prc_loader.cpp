@@ -17,6 +17,7 @@
 // types ...) is an error (PRGPU_EUNSUPPORTED) naming the block -- never silently dropped; blocks that do not influence the
 // radiance (outputs) are skipped with a warning.
 #include <algorithm>
+#include <array>
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -32,6 +33,7 @@
 #include <zlib.h>
 
 #include "datalisp.h"
+#include "image_reader.h"
 #include "setup.h"
 
 using prgpu_host::dl::Group;
@@ -254,8 +256,11 @@ struct Loader {
 			return spectrum_const((float)v.number());
 		if (v.type == Value::STRING) {
 			// SceneLoadContext::lookupSpectralNode (SceneLoadContext.cpp:222-232): a string names a (node ...)/(texture ...) block; an
-			// unknown name silently yields the parameter's default.  Named blocks are rejected when they are declared (dispatch), so
-			// every name is unknown here.
+			// unknown name silently yields the parameter's default.  (node ...) blocks are rejected when they are declared (dispatch), so
+			// every name but a declared texture's is unknown here.
+			const auto tex = texture_ids.find(v.s);
+			if (tex != texture_ids.end())
+				return tex->second;
 			warn(std::string(":") + key + " of " + where(owner) + " names the unknown node '" + v.s + "': default value used (as the reference does)");
 			return spectrum_const(string_default);
 		}
@@ -349,6 +354,8 @@ struct Loader {
 				fail(PRGPU_EUNSUPPORTED, where(e) + ": nested smul is not supported (operands must be leaves)");
 			if (out.spectra[s.lhs].kind == PRGPU_SPEC_CHECKER || out.spectra[s.rhs].kind == PRGPU_SPEC_CHECKER)
 				fail(PRGPU_EUNSUPPORTED, where(e) + ": a checkerboard inside smul is not supported");
+			if (out.spectra[s.lhs].kind == PRGPU_SPEC_IMAGE || out.spectra[s.rhs].kind == PRGPU_SPEC_IMAGE)
+				fail(PRGPU_EUNSUPPORTED, where(e) + ": an image texture inside smul is not supported");
 			return add_spectrum(s);
 		}
 		if (id == "lookup_index") { // ReflectiveNode.cpp:224-246,387-396: tabulated Sellmeier coefficients (refractiveindex.info)
@@ -503,7 +510,115 @@ struct Loader {
 			warn(where(e) + ": spd file '" + file + "' has non equidistant data (read as equidistant, as in the reference)");
 		return spectrum_table(start, end, values.data(), rows);
 	}
-	std::string current_dir; // directory of the file being loaded (relative file names of spd nodes)
+	// ---- (texture ...) blocks: TextureParser::parse (parser/TextureParser.cpp:60-207) ------------------------------------------
+	std::map<std::string, uint32_t> texture_ids; // name -> its PRGPU_SPEC_IMAGE node
+	static int wrap_mode(const Value& v) // parseWrap (:20-32): anything unknown is the default, black
+	{
+		const std::string w = v.type == Value::STRING ? lower(v.s) : std::string();
+		return w == "clamp" ? 1 : w == "periodic" ? 2 : w == "mirror" ? 3 : 0;
+	}
+	// the node of an image (height x width x 3 linear RGB, rows top-down): one four-float texel of coefficients per pixel, then the black texel
+	uint32_t spectrum_image(const float* rgb, uint32_t w, uint32_t h, int interpolation, int wrap_s, int wrap_t)
+	{
+		prgpu_spectrum s = blank(PRGPU_SPEC_IMAGE);
+		s.lhs			 = w;
+		s.rhs			 = h;
+		s.p[0]			 = (float)interpolation;
+		s.p[1]			 = (float)wrap_s;
+		s.p[2]			 = (float)wrap_t;
+		out.tables.resize((out.tables.size() + 3) / 4 * 4, 0.0f); // a texel is one aligned 16-byte record
+		const uint64_t n = uint64_t(w) * h + 1;
+		if (uint64_t(out.tables.size()) + 4 * n > 0xFFFFFFFFull)
+			fail(PRGPU_EUNSUPPORTED, "the scene's image textures exceed the table array");
+		s.table_offset = (uint32_t)out.tables.size();
+		s.table_count  = (uint32_t)(4 * n);
+		std::map<std::array<uint32_t, 3>, std::array<float, 3>> memo; // an 8-bit image has few distinct colours
+		const float black[3] = { 0.0f, 0.0f, 0.0f };
+		for (uint64_t i = 0; i < n; ++i) {
+			const float* px = i + 1 < n ? rgb + 3 * i : black;
+			std::array<uint32_t, 3> key;
+			std::memcpy(key.data(), px, 12);
+			auto it = memo.find(key);
+			if (it == memo.end()) {
+				std::array<float, 3> c;
+				prgpu_host::rgb_to_coeffs(px, c.data());
+				it = memo.emplace(key, c).first;
+			}
+			out.tables.insert(out.tables.end(), it->second.begin(), it->second.end());
+			out.tables.push_back(0.0f);
+		}
+		return add_spectrum(s);
+	}
+	void add_texture(const Group& g)
+	{
+		const std::string name = get_string(g, "name", "");
+		if (name.empty())
+			fail(PRGPU_EINVAL, where(g) + ": texture without a name");
+		const Value* fv = g.get("file");
+		if (!fv)
+			fv = g.get("filename");
+		if (!fv || fv->type != Value::STRING || fv->s.empty())
+			fail(PRGPU_EINVAL, where(g) + ": no valid filename given for texture '" + name + "'");
+		int wrap[3] = { 0, 0, 0 }; // s, t, r (the third is parsed and unused, as a 2D lookup leaves it)
+		if (const Value* wv = g.get("wrap")) {
+			if (wv->type == Value::STRING)
+				wrap[0] = wrap[1] = wrap[2] = wrap_mode(*wv);
+			else if (wv->type == Value::GROUP)
+				for (size_t i = 0; i < 3 && i < wv->g->anonymous_count(); ++i)
+					if (wv->g->at(i).type == Value::STRING)
+						wrap[i] = wrap_mode(wv->g->at(i));
+		}
+		int interpolation = 1;
+		{ // parseInterpolation (:48-58): bicubic and the default smart bicubic are not built
+			const Value* iv		 = g.get("interpolation");
+			const std::string in = iv && iv->type == Value::STRING ? lower(iv->s) : std::string();
+			if (in == "closest")
+				interpolation = 0;
+			else if (in != "bi" && in != "bilinear")
+				warn(where(g) + ": texture '" + name + "' asks for " + (in == "bicubic" ? "bicubic" : "the default smart bicubic") + " interpolation: bilinear is used (bicubic is not built)");
+		}
+		if (const Value* bv = g.get("blur")) { // :mip and :anisotropic change nothing: the reference looks textures up with zero derivatives
+			bool blurred = bv->is_number() && bv->number() != 0.0;
+			if (bv->type == Value::GROUP)
+				for (size_t i = 0; i < 3 && i < bv->g->anonymous_count(); ++i)
+					blurred = blurred || (bv->g->at(i).is_number() && bv->g->at(i).number() != 0.0);
+			if (blurred)
+				fail(PRGPU_EUNSUPPORTED, where(g) + ": texture '" + name + "': a non-zero :blur is not supported");
+		}
+		std::string path = fv->s;
+		if (path[0] != '/' && !current_dir.empty())
+			path = current_dir + "/" + path;
+		std::string type;
+		if (const Value* tv = g.get("type"); tv && tv->type == Value::STRING) {
+			type = lower(tv->s);
+		} else {
+			warn(where(g) + ": no valid type given for texture '" + name + "': assuming color");
+			type = "color";
+		}
+		if (texture_ids.count(name))
+			fail(PRGPU_EINVAL, where(g) + ": texture '" + name + "' already exists");
+		if (type == "scalar")
+			fail(PRGPU_EUNSUPPORTED, where(g) + ": texture '" + name + "': scalar textures are not supported");
+		if (type != "color" && type != "grayscale" && type != "spectral")
+			fail(PRGPU_EINVAL, where(g) + ": no known type given for texture '" + name + "'");
+		prgpu_host::Image img;
+		std::string err;
+		if (const int rc = prgpu_host::read_image(path.c_str(), img, false, err))
+			fail(rc, where(g) + ": texture '" + name + "': " + err);
+		for (float v : img.rgb)
+			if (!(v >= 0.0f))
+				fail(PRGPU_EINVAL, where(g) + ": texture '" + name + "': colour components must be finite and non-negative");
+		texture_ids[name] = spectrum_image(img.rgb.data(), img.width, img.height, interpolation, wrap[0], wrap[1]);
+	}
+	// an image texture, or a checkerboard that holds one
+	bool holds_image(uint32_t id, int depth = 0) const
+	{
+		if (id >= out.spectra.size() || depth > 64)
+			return false;
+		const prgpu_spectrum& n = out.spectra[id];
+		return n.kind == PRGPU_SPEC_IMAGE || (n.kind == PRGPU_SPEC_CHECKER && (holds_image(n.lhs, depth + 1) || holds_image(n.rhs, depth + 1)));
+	}
+	std::string current_dir; // directory of the file being loaded (relative file names of spd nodes and textures)
 	float string_default = 1.0f; // default of the parameter being parsed (for strings naming unknown nodes)
 	// FloatSpectralNode::eval of a loaded node at one wavelength (what SkyModel asks of the ground albedo, SkyModel.cpp:30-34): the
 	// arithmetic of spectrum_leaf / spectrum_eval on the device
@@ -801,6 +916,8 @@ struct Loader {
 			{ // the albedo is only evaluated here: nodes its expression created do not stay in the scene
 				const size_t n_spectra = out.spectra.size(), n_tables = out.tables.size();
 				const uint32_t alb	   = spectral_param(g, { "albedo" }, 0.15f);
+				if (holds_image(alb))
+					fail(PRGPU_EUNSUPPORTED, where(g) + ": image textures on infinite lights are not supported");
 				for (int k = 0; k < PRGPU_SKY_BANDS; ++k)
 					sp.albedo[k] = eval_spectrum_at(alb, 320.0f + k * 40.0f);
 				out.spectra.resize(n_spectra);
@@ -843,6 +960,8 @@ struct Loader {
 		} else {
 			fail(PRGPU_EUNSUPPORTED, where(g) + ": light type '" + type + "' is not supported (env/environment/background, distant/direction, sun, sky, uniform_sky and cloudy_sky are)");
 		}
+		if (l.kind != PRGPU_LIGHT_SKY && (holds_image(l.radiance) || holds_image(l.background)))
+			fail(PRGPU_EUNSUPPORTED, where(g) + ": image textures on infinite lights are not supported");
 		out.lights.push_back(l);
 	}
 	// OutputSpecification::parse (src/loader/output/io/OutputSpecification.cpp:254-365): the channels of one output file
@@ -1135,6 +1254,8 @@ struct Loader {
 		prgpu_emission e;
 		e.kind	   = PRGPU_EMS_DIFFUSE;
 		e.radiance = spectral_param(g, { "radiance" }, 1.0f);
+		if (holds_image(e.radiance))
+			fail(PRGPU_EUNSUPPORTED, where(g) + ": image textures on emissions are not supported");
 		emission_ids[name] = (uint32_t)out.emissions.size();
 		out.emissions.push_back(e);
 	}
@@ -1324,6 +1445,11 @@ struct Loader {
 			out.positions.insert(out.positions.end(), 9, 0.0f); // placeholder triangle
 			for (uint32_t i = 0; i < 3; ++i)
 				out.indices.push_back(base + i);
+			if (type == "sphere" && mat != PRGPU_INVALID_ID) {
+				const prgpu_material& m = out.materials[mat];
+				if (holds_image(m.albedo) || holds_image(m.ior) || holds_image(m.k) || holds_image(m.transmission))
+					fail(PRGPU_EUNSUPPORTED, where(g) + ": image textures on sphere entities are not supported (their uv needs atan2 / acos)");
+			}
 			out.tri_material.push_back(mat);
 			out.entities.push_back(e);
 			return;
@@ -1925,7 +2051,9 @@ struct Loader {
 			add_embed(b, dir);
 		else if (id == "light")
 			add_light(b);
-		else if (id == "texture" || id == "node")
+		else if (id == "texture")
+			add_texture(b);
+		else if (id == "node")
 			fail(PRGPU_EUNSUPPORTED, where(b) + ": block is not supported by this backend yet");
 		else if (id == "scene")
 			fail(PRGPU_EINVAL, where(b) + ": invalid inner scene entry");

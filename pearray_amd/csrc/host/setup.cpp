@@ -1086,8 +1086,23 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 	}
 	for (uint32_t i = 0; i < d->n_spectra; ++i) {
 		const prgpu_spectrum& n = d->spectra[i];
-		if (n.kind > PRGPU_SPEC_CHECKER)
+		if (n.kind > PRGPU_SPEC_IMAGE)
 			return bad("unknown spectrum kind");
+		if (n.kind == PRGPU_SPEC_IMAGE) {
+			if (n.lhs == 0 || n.rhs == 0 || n.lhs > 4096 || n.rhs > 4096)
+				return bad("image texture: width and height must be 1..4096");
+			const uint64_t need = 4 * (uint64_t(n.lhs) * n.rhs + 1);
+			if (n.table_offset % 4 != 0 || n.table_count != need || !d->spectral_tables || uint64_t(n.table_offset) + need > d->n_spectral_table_values)
+				return bad("image texture: 4 (W H + 1) floats at a table_offset that is a multiple of 4, inside spectral_tables");
+			if (!(n.p[0] == 0.0f || n.p[0] == 1.0f))
+				return bad("image texture: interpolation is 0 (closest) or 1 (bilinear)");
+			for (int k = 1; k <= 2; ++k)
+				if (!(n.p[k] == 0.0f || n.p[k] == 1.0f || n.p[k] == 2.0f || n.p[k] == 3.0f))
+					return bad("image texture: wrap is 0 (black), 1 (clamp), 2 (periodic) or 3 (mirror)");
+			for (uint64_t k = 0; k < need; ++k)
+				if (!std::isfinite(d->spectral_tables[n.table_offset + k]))
+					return bad("image texture: texel coefficients must be finite");
+		}
 		if (n.kind == PRGPU_SPEC_CHECKER && (n.lhs >= i || n.rhs >= i || !(n.p[2] == 0.0f || n.p[2] == 1.0f || n.p[2] == 2.0f)))
 			return bad("checkerboard operands must precede the node and its mode is 0, 1 or 2");
 		if (n.kind == PRGPU_SPEC_SELLMEIER && (n.table_count < 2 || n.table_count > 8 || (n.table_count & 1u) || uint64_t(n.table_offset) + n.table_count > d->n_spectral_table_values))
@@ -1101,6 +1116,8 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 				return bad("nested MUL spectral nodes are not supported", PRGPU_EUNSUPPORTED);
 			if (d->spectra[n.lhs].kind == PRGPU_SPEC_CHECKER || d->spectra[n.rhs].kind == PRGPU_SPEC_CHECKER)
 				return bad("a checkerboard inside a MUL node is not supported", PRGPU_EUNSUPPORTED);
+			if (d->spectra[n.lhs].kind == PRGPU_SPEC_IMAGE || d->spectra[n.rhs].kind == PRGPU_SPEC_IMAGE)
+				return bad("an image texture inside a MUL node is not supported", PRGPU_EUNSUPPORTED);
 		}
 	}
 	for (uint32_t i = 0; i < d->n_materials; ++i) {
@@ -1131,7 +1148,7 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 		}
 	}
 	{
-		auto textured = [&](uint32_t id) { return id != PRGPU_INVALID_ID && id < d->n_spectra && d->spectra[id].kind == PRGPU_SPEC_CHECKER; };
+		auto textured = [&](uint32_t id) { return id != PRGPU_INVALID_ID && id < d->n_spectra && (d->spectra[id].kind == PRGPU_SPEC_CHECKER || d->spectra[id].kind == PRGPU_SPEC_IMAGE); };
 		for (uint32_t i = 0; i < d->n_emissions; ++i)
 			if (textured(d->emissions[i].radiance))
 				return bad("textured emissions are not supported", PRGPU_EUNSUPPORTED);

@@ -548,6 +548,8 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 	for (uint32_t i = 0; i < d->n_spectra; ++i)
 		if (d->spectra[i].kind == PRGPU_SPEC_CHECKER)
 			sc.features |= prd::FEAT_TEXTURES;
+		else if (d->spectra[i].kind == PRGPU_SPEC_IMAGE) // the lookup lives in the top variant only
+			sc.features |= prd::FEAT_TEXTURES | prd::FEAT_IMAGES;
 	for (uint32_t e = 0; e < d->n_entities; ++e)
 		if (d->entities[e].has_uvs && d->uvs && d->entities[e].kind == PRGPU_ENTITY_MESH)
 			sc.features |= prd::FEAT_TEXTURES; // UV-derived tangent frames need the full variant
@@ -566,7 +568,7 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 		else if (d->entities[e].kind == PRGPU_ENTITY_DISK)
 			sc.features |= prd::FEAT_DISKS;
 	// measurement aid: run a scene with a larger kernel variant than it needs (same results; LPE and quadrics need data the scene does not have)
-	sc.features |= read_knobs().force_features & prd::FEAT_ALL & ~(prd::FEAT_LPE | prd::FEAT_QUADRICS | prd::FEAT_DISKS);
+	sc.features |= read_knobs().force_features & prd::FEAT_ALL & ~(prd::FEAT_LPE | prd::FEAT_QUADRICS | prd::FEAT_DISKS | prd::FEAT_IMAGES);
 	sc.scene_radius	 = t.scene_radius;
 	sc.wl_cdf_size	 = (uint32_t)t.wl_cdf.size();
 	sc.wl_u_offset	 = t.wl_u_offset;

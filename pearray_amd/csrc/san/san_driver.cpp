@@ -1,11 +1,14 @@
 // san_driver.cpp -- host of the sanitizer build (`make san`): the library's host-side readers of FOREIGN files -- the .prc scene language
 // (host/datalisp.cpp, host/prc_loader.cpp: inline meshes, (embed) of Wavefront OBJ, PLY and Mitsuba-serialized archives, (include)) with
 // everything they call (sky tables, colour fits, light path expressions, the EXR writer) -- compiled with -fsanitize=address,undefined
-// and driven over a list of scene files.  No device code is involved: these translation units are plain C++.
+// and driven over a list of scene files; and the reader of the image files (texture ...) blocks name (host/image_reader.cpp: PNG, PFM).
+// No device code is involved: these translation units are plain C++.
 // The reference's counterparts: src/loader/SceneLoader.cpp:44-72,775-846, src/loader/archives/{WavefrontLoader,PlyLoader,MtsSerializedLoader}.cpp.
 //
 //   prc_san <file.prc> ...        load each file, walk the description it yields, free it; one status line per file on stdout
 //   prc_san -                     the same for the paths read from stdin (one per line): tools/fuzz_loader.py feeds it thousands of mutants
+//   prc_san --image <file> ... | -   the image reader alone on each file (prgpu_image_load: the size query, then the pixels, all of them read);
+//                                 tools/fuzz_image.py feeds it mutants of its own PNG and PFM seeds
 // Exit code 0 unless a sanitizer aborts the process (ASan / UBSan run with halt_on_error, see the Makefile).
 #include <cstdint>
 #include <cstdio>
@@ -87,8 +90,36 @@ static void one(const std::string& path)
 		prgpu_prc_free(scene);
 }
 
+static void one_image(const std::string& path)
+{
+	uint32_t w = 0, h = 0, ch = 0;
+	int lin	   = 0;
+	int rc	   = prgpu_image_load(path.c_str(), &w, &h, &ch, &lin, nullptr);
+	double sum = 0.0;
+	if (rc == PRGPU_OK) {
+		std::vector<float> rgb(size_t(w) * h * 3);
+		rc = prgpu_image_load(path.c_str(), &w, &h, &ch, &lin, rgb.data());
+		for (float v : rgb)
+			sum += v;
+	}
+	std::printf("%d %u %u %u %d %.9g | %s\n", rc, w, h, ch, lin, sum, path.c_str());
+}
+
 int main(int argc, char** argv)
 {
+	if (argc >= 2 && std::string(argv[1]) == "--image") {
+		std::string line;
+		if (argc == 3 && std::string(argv[2]) == "-") {
+			while (std::getline(std::cin, line))
+				if (!line.empty())
+					one_image(line);
+		} else {
+			for (int i = 2; i < argc; ++i)
+				one_image(argv[i]);
+		}
+		std::fflush(stdout);
+		return 0;
+	}
 	if (argc == 2 && std::string(argv[1]) == "-") {
 		std::string line;
 		while (std::getline(std::cin, line))

@@ -31,6 +31,18 @@ def rgb_to_coeffs(rgb):
     return [dst[0], dst[1], dst[2]]
 
 
+def load_image(path):
+    """An image file as a `(texture ...)` block reads it (prgpu_image_load: PNG or PFM): (float32 [H, W, 3] linear RGB with rows
+    top-down, channels in the file, whether the samples were linearised)."""
+    lib = abi.load()
+    w, h, ch, lin = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_int()
+    args = (os.fsencode(path), C.byref(w), C.byref(h), C.byref(ch), C.byref(lin))
+    abi.check(lib.prgpu_image_load(*args, None))
+    rgb = np.zeros((h.value, w.value, 3), np.float32)
+    abi.check(lib.prgpu_image_load(*args, rgb.ctypes.data_as(C.POINTER(C.c_float))))
+    return rgb, ch.value, bool(lin.value)
+
+
 class SceneBuilder:
     def __init__(self, width, height):
         self.settings = abi.default_settings(width, height)
@@ -111,6 +123,26 @@ class SceneBuilder:
 
     def smul(self, a, b):
         return self._add_spec(kind=abi.SPEC_MUL, lhs=a, rhs=b)
+
+    IMAGE_WRAPS = {"black": 0, "clamp": 1, "periodic": 2, "mirror": 3}
+
+    def image_texture(self, rgb, interpolation="bilinear", wrap="black"):
+        """(texture :type 'color' ...), TextureParser.cpp:60-207: `rgb` is a linear float image [H, W, 3], rows top-down (what
+        prgpu_image_load returns); `interpolation` is 'closest' or 'bilinear' ('bi'), `wrap` one of IMAGE_WRAPS or a pair (s, t).
+        Returns the id of a PRGPU_SPEC_IMAGE node: W*H + 1 texels of four floats (the coefficients of the pixel, 0), the last one black."""
+        rgb = np.asarray(rgb, dtype=np.float32)
+        assert rgb.ndim == 3 and rgb.shape[2] == 3 and 1 <= rgb.shape[0] <= 4096 and 1 <= rgb.shape[1] <= 4096
+        interp = {"closest": 0, "bi": 1, "bilinear": 1}[interpolation.lower()]
+        ws, wt = (wrap, wrap) if isinstance(wrap, str) else wrap
+        h, w = rgb.shape[:2]
+        pixels = np.concatenate([rgb.reshape(-1, 3), np.zeros((1, 3), np.float32)])[None]     # ... and the black texel
+        texels = np.zeros((h * w + 1, 4), np.float32)
+        texels[:, :3] = self.rgb_image_to_coefficients(pixels)[0]
+        self.tables.extend([0.0] * (-len(self.tables) % 4))                                   # a texel is one aligned 16-byte record
+        off = len(self.tables)
+        self.tables.extend(texels.reshape(-1).tolist())
+        return self._add_spec(kind=abi.SPEC_IMAGE, lhs=w, rhs=h, table_offset=off, table_count=4 * (h * w + 1),
+                              p=[float(interp), float(self.IMAGE_WRAPS[ws.lower()]), float(self.IMAGE_WRAPS[wt.lower()])])
 
     # ---- materials / emissions ---------------------------------------------------------------------
     def lambert(self, albedo, two_sided=True):
