@@ -50,7 +50,8 @@ extern "C" {
 
 #define PRGPU_API_VERSION 8 /* layout version of the structs below (prgpu_scene_desc::api_version); entry points added since keep it: round 5 added
                                prgpu_pipeline_info_get, prgpu_comm_query, prgpu_reduced_planes; PRGPU_ENTITY_DISK and PRGPU_SPEC_IMAGE are new enumerators, no field moved;
-                               prgpu_image_load came with the latter */
+                               prgpu_image_load came with the latter; PRGPU_MAT_OREN_NAYAR, PRGPU_MAT_NULL, PRGPU_MAT_BLEND and PRGPU_MAT_ADD are new
+                               enumerators that reuse fields of prgpu_material, no field moved */
 #define PRGPU_INVALID_ID 0xFFFFFFFFu /* PR_INVALID_ID, src/base/config/Constants.inl:6 */
 
 enum {
@@ -115,6 +116,17 @@ enum { PRGPU_MAT_LAMBERT = 0, PRGPU_MAT_DIELECTRIC = 1, PRGPU_MAT_CONDUCTOR = 2,
        PRGPU_MAT_PRINCIPLED = 5,
        PRGPU_MAT_MIRROR = 6 };           /* mirror.cpp: delta reflection weighted by `specularity` (albedo), no Fresnel term */       /* principled.cpp: Disney-style diffuse / retro / sheen / GGX specular / refraction / clearcoat lobes with a
                                             four-way lobe selection (principled.cpp:111-139,418-435); constant scalar parameters only */
+/* OREN_NAYAR  src/plugins/main/materials/orennayar.cpp (`orennayar`, `oren`, `rough`): the "improved" Oren-Nayar diffuse term, albedo (A + B s / t) with
+ *             sigma^2 = roughness^2, s = V.L - NdotL NdotV, t = 1 when s < eps else max(NdotL, NdotV); `albedo` and `roughness_x`; one sided: no light
+ *             from below the normal (max(0, NdotL)), its samples are NOT flipped to the viewer's side, and there is no `two_sided`
+ * NULL        null.cpp: delta-only, passes the ray on unchanged (L = -V, weight 1, pdf 1, specular transmission); draws nothing
+ * BLEND       blend.cpp (`blend`, `mix`): two EARLIER materials of the array, neither a BLEND / ADD itself, and a factor f clamped to [0, 1] at
+ *             evaluation: eval (1 - f) w1 + f w2 (weight and pdf alike; a delta-only child drops out and the other keeps its factor), sample: one
+ *             number picks child 1 when it is < 1 - f, and the child's integral weight AND pdf are scaled by its selection probability
+ * ADD         add.cpp: the same structure: eval w1 + w2 with the mean of the pdfs (one delta-only child: the other's weight, half its pdf),
+ *             sample: one number against 0.5 picks the child, whose pdf is halved and whose weight is kept
+ * A BLEND / ADD whose two children are delta-only is delta-only itself. */
+enum { PRGPU_MAT_OREN_NAYAR = 7, PRGPU_MAT_NULL = 8, PRGPU_MAT_BLEND = 9, PRGPU_MAT_ADD = 10 };
 enum { PRGPU_MATF_ANISOTROPIC = 1u,      /* roughness_y given as its own parameter (the reference compares the NODES, not the values) */
        PRGPU_MATF_NO_VNDF = 2u,          /* `:vndf false`: sample the plain GGX normal distribution (Microfacet.h:225-256; the anisotropic form
                                             through the backend's shared fp32 tan / atan) */
@@ -125,14 +137,16 @@ enum { PRGPU_PRINCIPLED_DIFFUSE_TRANSMISSION = 0, PRGPU_PRINCIPLED_SPECULAR_TRAN
        PRGPU_PRINCIPLED_SHEEN_TINT = 7, PRGPU_PRINCIPLED_CLEARCOAT = 8, PRGPU_PRINCIPLED_CLEARCOAT_GLOSS = 9, PRGPU_PRINCIPLED_COUNT = 10 };
 typedef struct prgpu_material {
 	uint32_t kind;
-	uint32_t albedo;       /* spectrum index.  LAMBERT: `albedo`; every other kind: `specularity` (reflection tint, default 1) */
-	uint32_t two_sided;    /* LAMBERT `two_sided`, default true (lambert.cpp:108) */
+	uint32_t albedo;       /* spectrum index.  LAMBERT, OREN_NAYAR: `albedo`; every other kind: `specularity` (reflection tint, default 1);
+	                          NULL, BLEND, ADD: any valid index (not read) */
+	uint32_t two_sided;    /* LAMBERT `two_sided`, default true (lambert.cpp:108); BLEND, ADD: material index of `material1` (smaller than the combinator's own) */
 	uint32_t ior;          /* (ROUGH_)DIELECTRIC: `index`/`eta`/`ior` spectrum (default 1.55); (ROUGH_)CONDUCTOR: `eta` (default 1.2) */
 	uint32_t transmission; /* (ROUGH_)DIELECTRIC: `transmission` tint spectrum, or PRGPU_INVALID_ID = same as specularity (dielectric.cpp:92-96) */
-	uint32_t thin;         /* DIELECTRIC: `thin` sheet approximation (dielectric.cpp:69-72,98-101); PRINCIPLED: `thin` */
+	uint32_t thin;         /* DIELECTRIC: `thin` sheet approximation (dielectric.cpp:69-72,98-101); PRINCIPLED: `thin`; BLEND, ADD: material index of `material2` */
 	uint32_t k;            /* (ROUGH_)CONDUCTOR: `k`/`kappa` absorption index spectrum (default 2.605) */
 	uint32_t flags;        /* PRGPU_MATF_* (rough kinds) */
-	float roughness_x;     /* rough kinds: `roughness_x` or `roughness` (constant scalar; textures are out of scope) */
+	float roughness_x;     /* rough kinds: `roughness_x` or `roughness` (constant scalar; textures are out of scope); OREN_NAYAR: `roughness` (default 0.5);
+	                          BLEND: `factor` as given (default 0.5; finite; clamped to [0, 1] where it is evaluated) */
 	float roughness_y;     /* rough kinds: `roughness_y`; ignored (= roughness_x) unless PRGPU_MATF_ANISOTROPIC */
 	float principled[PRGPU_PRINCIPLED_COUNT]; /* PRINCIPLED: albedo = `base`/`base_color` (default 0.8), ior (1.55), roughness_x = `roughness` (0.5),
 	                                             thin = `thin`, and these scalars */
@@ -426,6 +440,7 @@ typedef struct prgpu_pipeline_info {
 	uint32_t bvh_top;              /* the top of the tree (the sort key's entity field): 0 = the entities in the order of the scene description, 1 = by a surface-area tree over their boxes, 2 = in the Morton order of their centres; the builder builds all three and keeps the cheapest tree */
 	uint32_t bvh_stack_bound;      /* entries the deepest walk of the tree can hold on a lane's traversal stack (a scene whose tree needs more than the stack holds is refused) */
 	float    bvh_cost_4_wide, bvh_cost_6_wide; /* the builder's estimate for either tree: inner records a ray through the scene's box visits (0: not computed) */
+	uint32_t variant;              /* which compiled variant of the path kernel the scene's features select, 1 (lean) .. 5 (everything: light path expressions, quadrics, disks, image textures, the Oren-Nayar / null / blend / add materials); took the struct's tail padding, no field moved */
 } prgpu_pipeline_info;
 int  prgpu_pipeline_info_get(prgpu_scene* s, prgpu_pipeline_info* out);
 /* Enable/disable node+triangle counting inside the traversal kernels (slower; default off). */

@@ -15,6 +15,7 @@ COMM_ID_BYTES = 128
 
 SPEC_CONST, SPEC_PARAMETRIC, SPEC_PARAMETRIC_SCALED, SPEC_TABLE, SPEC_MUL, SPEC_SELLMEIER, SPEC_CHECKER, SPEC_IMAGE = range(8)
 MAT_LAMBERT, MAT_DIELECTRIC, MAT_CONDUCTOR, MAT_ROUGH_CONDUCTOR, MAT_ROUGH_DIELECTRIC, MAT_PRINCIPLED, MAT_MIRROR = 0, 1, 2, 3, 4, 5, 6
+MAT_OREN_NAYAR, MAT_NULL, MAT_BLEND, MAT_ADD = 7, 8, 9, 10   # BLEND / ADD: two_sided, thin = the two children's material indices, roughness_x = the blend factor
 MATF_ANISOTROPIC, MATF_NO_VNDF, MATF_HAS_TRANSMISSION = 1, 2, 4
 PRINCIPLED_PARAMS = ("diffuse_transmission", "specular_transmission", "specular_tint", "anisotropic", "flatness", "metallic", "sheen",
                      "sheen_tint", "clearcoat", "clearcoat_gloss")
@@ -157,7 +158,8 @@ def default_settings(width, height):
 class PipelineInfo(C.Structure):  # prgpu_pipeline_info
     _fields_ = [("mode", C.c_uint32), ("shader_waves", C.c_int32), ("shading_share", C.c_float), ("calibration_launches", C.c_uint32),
                 ("kernel", C.c_uint32), ("blocks", C.c_uint32), ("slots_per_block", C.c_uint32), ("launches", C.c_uint64),
-                ("bvh_width", C.c_uint32), ("bvh_top", C.c_uint32), ("bvh_stack_bound", C.c_uint32), ("bvh_cost_4_wide", C.c_float), ("bvh_cost_6_wide", C.c_float)]
+                ("bvh_width", C.c_uint32), ("bvh_top", C.c_uint32), ("bvh_stack_bound", C.c_uint32), ("bvh_cost_4_wide", C.c_float), ("bvh_cost_6_wide", C.c_float),
+                ("variant", C.c_uint32)]
 
 
 class SkyParams(C.Structure):  # prgpu_sky_params

@@ -1410,6 +1410,23 @@ static __device__ PR_CLOSURE V3 principled_sample(const Principled& c, uint64_t&
 #define PR_CLOSURES_IMG 1
 #include "rough_closures.inl"
 #undef PR_CLOSURES_IMG
+// OrenNayarMaterial::calc (orennayar.cpp:29-47), the "improved" Oren-Nayar term: albedo (A + B s / t), sigma^2 = roughness^2.  NdotL is the
+// CLAMPED cosine the callers pass (max(0, L.z)); V.L takes the direction as it is.
+__device__ __forceinline__ Blob oren_nayar_calc(const Blob& albedo, float roughness, V3 Vt, V3 Lt, float NdotL)
+{
+	const float r2 = roughness * roughness;
+	Blob weight	   = albedo;
+	if (r2 > PR_EPS) {
+		const float s = -NdotL * Vt.z + dot(Vt, Lt);
+		const float t = s < PR_EPS ? 1.0f : fmaxf(NdotL, Vt.z);
+		const float a = 1 - 0.5f * r2 / (r2 + 0.33f);
+		const float B = 0.45f * r2 / (r2 + 0.09f);
+		const float b = B * s / t;
+		for (int i = 0; i < 4; ++i)
+			weight.v[i] *= (a + 0.17f * albedo.v[i] * r2 / (r2 + 0.13f)) + b;
+	}
+	return weight;
+}
 // IMaterial::eval for next event estimation: LambertMaterial::eval (lambert.cpp:33-42) inline, the rough closures out of line
 template <uint32_t FEATS>
 __device__ __forceinline__ void material_eval(const DevScene& s, const prgpu_material& mat, const Blob& albedo, const Blob& wl, const Blob& cie_y, V3 Vt, V3 Lt, Blob& weight, Blob& pdf, bool& delta,
@@ -1422,11 +1439,92 @@ __device__ __forceinline__ void material_eval(const DevScene& s, const prgpu_mat
 			rough_eval(s, mat, wl, cie_y, Vt, Lt, weight, pdf, delta);
 		return;
 	}
+	if ((FEATS & FEAT_MIX_MATERIALS) && mat.kind == PRGPU_MAT_OREN_NAYAR) { // OrenNayarMaterial::eval (orennayar.cpp:49-58): one sided, no hemisphere test
+		delta		   = false;
+		const float dt = fmaxf(0.0f, Lt.z);
+		weight		   = (oren_nayar_calc(albedo, mat.roughness_x, Vt, Lt, dt) * PR_INV_PI_F) * dt;
+		pdf			   = blob(dt * PR_INV_PI_F);
+		return;
+	}
 	delta			= false;
 	const bool same = signbit(Vt.z) == signbit(Lt.z);
 	const float dt	= same ? (mat.two_sided ? fabsf(Lt.z) : fmaxf(0.0f, Lt.z)) : 0.0f;
 	weight			= (albedo * dt) * PR_INV_PI_F;
 	pdf				= blob(dt * PR_INV_PI_F);
+}
+// ---- BlendMaterial / AddMaterial (blend.cpp, add.cpp): the FEAT_MIX_MATERIALS builds only.  A combinator's record names its two children
+// (two_sided = material1, thin = material2: plain materials with a smaller index) and, for BLEND, the factor (roughness_x).
+// IMaterial::hasOnlyDeltaDistribution of a plain kind
+__device__ __forceinline__ bool mix_delta_only(uint32_t kind) { return kind == PRGPU_MAT_DIELECTRIC || kind == PRGPU_MAT_CONDUCTOR || kind == PRGPU_MAT_MIRROR || kind == PRGPU_MAT_NULL; }
+// a child as the vertex would have loaded it had the triangle named it: textures resolved at `uv`, albedo at the path's wavelengths
+template <uint32_t FEATS>
+__device__ __forceinline__ void mix_child(const DevScene& sc, uint32_t id, const Blob& wl, const float* uv, prgpu_material& m, Blob& albedo, bool& rough)
+{
+	const DevMaterial& dm = sc.materials[id];
+	m					  = dm.m;
+	if ((FEATS & FEAT_TEXTURES) && (sc.features & FEAT_TEXTURES)) {
+		m.albedo	   = resolve_texture(sc, m.albedo, uv);
+		m.ior		   = resolve_texture(sc, m.ior, uv);
+		m.k			   = resolve_texture(sc, m.k, uv);
+		m.transmission = resolve_texture(sc, m.transmission, uv);
+	}
+	rough  = (FEATS & FEAT_ROUGH_MATERIALS) && (m.kind == PRGPU_MAT_ROUGH_CONDUCTOR || m.kind == PRGPU_MAT_ROUGH_DIELECTRIC || m.kind == PRGPU_MAT_PRINCIPLED);
+	albedo = rough ? blob(0) : albedo_eval<(FEATS & FEAT_IMAGES) != 0u>(sc, m, dm.albedo, dm.m.albedo, wl, uv);
+}
+// IMaterial::eval of the vertex's material for next event estimation in the FEAT_MIX_MATERIALS builds (the others call material_eval, as
+// before).  Without a combinator this is material_eval.  With one
+// (BlendMaterial::eval, blend.cpp:41-75; AddMaterial::eval, add.cpp:40-66) the children that are not delta-only are evaluated, ONE call
+// site in a loop, and combined: (1 - f) w1 + f w2 for weight and pdf, resp. w1 + w2 with the pdfs' mean; with one delta-only child the other
+// one alone, scaled by its factor resp. with half its pdf, and with ITS delta flag (the two-children forms never set one).  sym_kind /
+// sym_roughness: kind and roughness_x of the material whose scattering type the pair reports (blend: child 1 when f <= 0.5; add: child 1).
+template <uint32_t FEATS>
+__device__ __forceinline__ void vertex_eval(const DevScene& sc, const prgpu_material& mat, const Blob& albedo, bool comb, bool delta1, bool delta2, const Blob& wl, const Blob& cie_y, V3 Vt,
+											V3 Lt, Blob& weight, Blob& pdf, bool& delta, uint32_t& sym_kind, float& sym_roughness, const float* uv)
+{
+	const bool add	 = mat.kind == PRGPU_MAT_ADD;
+	const float f	 = fminf(1.0f, fmaxf(0.0f, mat.roughness_x));
+	const bool both	 = comb && !delta1 && !delta2;
+	const int sym_of = !comb ? 0 : (both ? ((add || f <= 0.5f) ? 0 : 1) : (delta1 ? 1 : 0));
+	weight			 = blob(0);
+	pdf				 = blob(0);
+	delta			 = false;
+	const int n		 = comb ? 2 : 1;
+#pragma unroll 1
+	for (int c = 0; c < n; ++c) {
+		if (comb && (c ? delta2 : delta1))
+			continue;
+		prgpu_material cm;
+		Blob ca;
+		if (comb) {
+			bool rough;
+			mix_child<FEATS>(sc, c ? mat.thin : mat.two_sided, wl, uv, cm, ca, rough);
+		} else {
+			cm = mat;
+			ca = albedo;
+		}
+		Blob w, p;
+		bool d;
+		material_eval<FEATS>(sc, cm, ca, wl, cie_y, Vt, Lt, w, p, d, uv);
+		const float sw = (!comb || add) ? 1.0f : (c ? f : 1 - f);
+		const float sp = !comb ? 1.0f : (add ? (both ? 1.0f : 0.5f) : sw);
+		if (!comb) {
+			weight = w;
+			pdf	   = p;
+		} else {
+			for (int i = 0; i < 4; ++i) {
+				weight.v[i] += w.v[i] * sw;
+				pdf.v[i] += p.v[i] * sp;
+			}
+		}
+		if (!both)
+			delta = d;
+		if (c == sym_of) {
+			sym_kind	  = cm.kind;
+			sym_roughness = cm.roughness_x;
+		}
+	}
+	if (both && add)
+		pdf = pdf / 2.0f;
 }
 
 // CIESimpleSkyLight::radiance (cie_sky.cpp:108-126) for a world direction; (z + 1.01)^10 by squaring in fp32
@@ -1580,19 +1678,23 @@ __device__ __forceinline__ void inf_light_sample(const DevScene& sc, const DevIn
 // The MaterialScatteringType a material reports for the pair (V, L) in tangent space, as a path token symbol: lambert.cpp:41,69 diffuse
 // reflection; conductor.cpp:40,70, mirror.cpp:35,57, roughconductor.cpp:44,108 specular reflection; dielectric.cpp:79-107 and
 // roughdielectric.cpp:198-252 specular reflection / transmission by hemisphere; principled.cpp:511-521,565-575 by hemisphere and
-// roughness < 0.5.
-__device__ __forceinline__ uint32_t scatter_symbol(const prgpu_material& m, V3 Vt, V3 Lt)
+// roughness < 0.5; orennayar.cpp:56,78 diffuse reflection; null.cpp:52 specular transmission.  A blend / add reports the type of one of its
+// children (vertex_eval; the child that sampled): the callers pass that child's kind and roughness.
+__device__ __forceinline__ uint32_t scatter_symbol(uint32_t kind, float roughness_x, V3 Vt, V3 Lt)
 {
 	const bool same = sv_same_hemisphere(Vt, Lt);
-	switch (m.kind) {
-	case PRGPU_MAT_LAMBERT: return LPE_SYM_DIFFUSE_REFLECTION;
+	switch (kind) {
+	case PRGPU_MAT_LAMBERT:
+	case PRGPU_MAT_OREN_NAYAR: return LPE_SYM_DIFFUSE_REFLECTION;
+	case PRGPU_MAT_NULL: return LPE_SYM_SPECULAR_TRANSMISSION;
 	case PRGPU_MAT_DIELECTRIC:
 	case PRGPU_MAT_ROUGH_DIELECTRIC: return same ? LPE_SYM_SPECULAR_REFLECTION : LPE_SYM_SPECULAR_TRANSMISSION;
 	case PRGPU_MAT_PRINCIPLED:
-		return m.roughness_x < 0.5f ? (same ? LPE_SYM_SPECULAR_REFLECTION : LPE_SYM_SPECULAR_TRANSMISSION) : (same ? LPE_SYM_DIFFUSE_REFLECTION : LPE_SYM_DIFFUSE_TRANSMISSION);
+		return roughness_x < 0.5f ? (same ? LPE_SYM_SPECULAR_REFLECTION : LPE_SYM_SPECULAR_TRANSMISSION) : (same ? LPE_SYM_DIFFUSE_REFLECTION : LPE_SYM_DIFFUSE_TRANSMISSION);
 	default: return LPE_SYM_SPECULAR_REFLECTION; // conductor, mirror, rough conductor
 	}
 }
+__device__ __forceinline__ uint32_t scatter_symbol(const prgpu_material& m, V3 Vt, V3 Lt) { return scatter_symbol(m.kind, m.roughness_x, Vt, Lt); }
 
 // RenderTileSession::pushSPFragment (:55) of a path's first vertex (shade_vertex, and k_ao_hits of the `ao` integrator): the pixel's sample
 // count and, in kernels that hold the AOV code, the shading-point sums (LocalFrameOutputDevice::commitShadingPoints,
@@ -1776,7 +1878,9 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 		if (go_on) {
 			const DevMaterial& dmat = sc.materials[gp.material];
 			prgpu_material mat		= dmat.m;
-			if ((FEATS & FEAT_TEXTURES) && (sc.features & FEAT_TEXTURES)) { // ShadingContext::UV driven nodes
+			constexpr bool MIX		= (FEATS & FEAT_MIX_MATERIALS) != 0u; // Oren-Nayar, null, blend and add materials
+			const bool comb			= MIX && (mat.kind == PRGPU_MAT_BLEND || mat.kind == PRGPU_MAT_ADD); // its fields name two children, not spectra
+			if ((FEATS & FEAT_TEXTURES) && (sc.features & FEAT_TEXTURES) && !comb) { // ShadingContext::UV driven nodes
 				mat.albedo		 = resolve_texture(sc, mat.albedo, gp.uv);
 				mat.ior			 = resolve_texture(sc, mat.ior, gp.uv);
 				mat.k			 = resolve_texture(sc, mat.k, gp.uv);
@@ -1786,12 +1890,16 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 			uint64_t rnd			 = ps.rng[pixel];
 			const bool deltaMat		 = (FEATS & FEAT_DELTA_MATERIALS) && (mat.kind == PRGPU_MAT_DIELECTRIC || mat.kind == PRGPU_MAT_CONDUCTOR || mat.kind == PRGPU_MAT_MIRROR); // IMaterial::hasOnlyDeltaDistribution
 			const bool roughMat		 = (FEATS & FEAT_ROUGH_MATERIALS) && (mat.kind == PRGPU_MAT_ROUGH_CONDUCTOR || mat.kind == PRGPU_MAT_ROUGH_DIELECTRIC || mat.kind == PRGPU_MAT_PRINCIPLED);
+			// what guards next event estimation and the Russian roulette draw: a blend / add is delta-only when both children are
+			// (blend.cpp:156-173, add.cpp:141-158).  (These stay constants of the kernels without FEAT_MIX_MATERIALS: their code does not change.)
+			const bool delta1 = comb && mix_delta_only(sc.materials[mat.two_sided].m.kind), delta2 = comb && mix_delta_only(sc.materials[mat.thin].m.kind);
+			const bool deltaOnly = comb ? (delta1 && delta2) : (deltaMat || (MIX && mat.kind == PRGPU_MAT_NULL));
 			const Blob cie_y_blob	 = blob4(cie.y[0], cie.y[1], cie.y[2], cie.y[3]);
 			// albedo / specularity at the path's wavelengths, once: IMaterial::eval and ::sample of a vertex evaluate the same node at
 			// the same wavelengths (lambert.cpp:38,66; mirror / conductor / dielectric sample).  The rough closures fetch their own.
 			constexpr bool IMG	= (FEATS & FEAT_IMAGES) != 0u; // material parameters may be image textures: their evaluation takes the point's uv
-			const Blob albedo_v = roughMat ? blob(0) : albedo_eval<IMG>(sc, mat, dmat.albedo, dmat.m.albedo, wl, gp.uv);
-			if (cfg.nee && !deltaMat && !hasEmission && (sc.n_lights + ((FEATS & FEAT_INFINITE_LIGHTS) ? sc.n_inf_lights : 0u))) { // direct.cpp:100-101
+			Blob albedo_v		= roughMat ? blob(0) : albedo_eval<IMG>(sc, mat, dmat.albedo, dmat.m.albedo, wl, gp.uv);
+			if (cfg.nee && !deltaOnly && !hasEmission && (sc.n_lights + ((FEATS & FEAT_INFINITE_LIGHTS) ? sc.n_inf_lights : 0u))) { // direct.cpp:100-101
 				// ---- handleNEE
 				do {
 					float selPdf;
@@ -1823,7 +1931,12 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 						const V3 Lt = to_tangent_space(N, gp.Nx, gp.Ny, L);
 						Blob weight, bsdf_pdf;
 						bool evalDelta;
-						material_eval<FEATS>(sc, mat, albedo_v, wl, cie_y_blob, Vt, Lt, weight, bsdf_pdf, evalDelta, gp.uv);
+						uint32_t sym_kind	= 0u; // (FEAT_MIX_MATERIALS) the material whose scattering type the connection reports: a blend / add names one of its children
+						float sym_roughness = 0.0f;
+						if constexpr (MIX)
+							vertex_eval<FEATS>(sc, mat, albedo_v, comb, delta1, delta2, wl, cie_y_blob, Vt, Lt, weight, bsdf_pdf, evalDelta, sym_kind, sym_roughness, gp.uv);
+						else
+							material_eval<FEATS>(sc, mat, albedo_v, wl, cie_y_blob, Vt, Lt, weight, bsdf_pdf, evalDelta, gp.uv);
 						if (evalDelta) // direct.cpp:269-270
 							break;
 						const Blob bsdfWvlPdfS = bsdf_pdf * hf;
@@ -1867,7 +1980,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 							want_shadow = true;
 							sh_o		= make_float4(so.x, so.y, so.z, SHADOW_RAY_MIN);
 							sh_d		= make_float4(L.x, L.y, L.z, sh_far);
-							const uint32_t m_nee = with_lpe ? lpe_accepting(ps.lpe, lpe_step(ps.lpe, lpe_step(ps.lpe, lpe, scatter_symbol(mat, Vt, Lt)), LPE_SYM_BACKGROUND)) : 0u; // direct.cpp:338-342
+							const uint32_t m_nee = with_lpe ? lpe_accepting(ps.lpe, lpe_step(ps.lpe, lpe_step(ps.lpe, lpe, scatter_symbol(MIX ? sym_kind : mat.kind, MIX ? sym_roughness : mat.roughness_x, Vt, Lt)), LPE_SYM_BACKGROUND)) : 0u; // direct.cpp:338-342
 							sh_xyz		= make_float4(xyz_vis[0], xyz_vis[1], xyz_vis[2], __uint_as_float(fb_vis | (fb_occ << 8) | (m_nee << 16)));
 						} else {
 							apply_fragment(ps, pixel, entry, fb_occ, xyz_occ);
@@ -1933,7 +2046,12 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 					const V3 Lt = to_tangent_space(N, gp.Nx, gp.Ny, L);
 					Blob weight, bsdf_pdf;
 					bool evalDelta;
-					material_eval<FEATS>(sc, mat, albedo_v, wl, cie_y_blob, Vt, Lt, weight, bsdf_pdf, evalDelta, gp.uv);
+					uint32_t sym_kind	= 0u; // (FEAT_MIX_MATERIALS) the material whose scattering type the connection reports: a blend / add names one of its children
+					float sym_roughness = 0.0f;
+					if constexpr (MIX)
+						vertex_eval<FEATS>(sc, mat, albedo_v, comb, delta1, delta2, wl, cie_y_blob, Vt, Lt, weight, bsdf_pdf, evalDelta, sym_kind, sym_roughness, gp.uv);
+					else
+						material_eval<FEATS>(sc, mat, albedo_v, wl, cie_y_blob, Vt, Lt, weight, bsdf_pdf, evalDelta, gp.uv);
 					if (evalDelta) // direct.cpp:269-270
 						break;
 					const Blob bsdfWvlPdfS = bsdf_pdf * hf;
@@ -1972,7 +2090,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 						want_shadow = true;
 						sh_o		= make_float4(so.x, so.y, so.z, SHADOW_RAY_MIN);
 						sh_d		= make_float4(L.x, L.y, L.z, distance);
-						const uint32_t m_nee = with_lpe ? lpe_accepting(ps.lpe, lpe_step(ps.lpe, lpe_step(ps.lpe, lpe, scatter_symbol(mat, Vt, Lt)), LPE_SYM_EMISSIVE)) : 0u; // direct.cpp:338-345
+						const uint32_t m_nee = with_lpe ? lpe_accepting(ps.lpe, lpe_step(ps.lpe, lpe_step(ps.lpe, lpe, scatter_symbol(MIX ? sym_kind : mat.kind, MIX ? sym_roughness : mat.roughness_x, Vt, Lt)), LPE_SYM_EMISSIVE)) : 0u; // direct.cpp:338-345
 						sh_xyz		= make_float4(xyz_vis[0], xyz_vis[1], xyz_vis[2], __uint_as_float(fb_vis | (fb_occ << 8) | (m_nee << 16)));
 					} else {
 						apply_fragment(ps, pixel, entry, fb_occ, xyz_occ);
@@ -1982,7 +2100,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 			flags = hasEmission ? (flags | FLAG_LAST_EMISSIVE) : (flags & ~FLAG_LAST_EMISSIVE);
 
 			// ---- handleScattering
-			const float scatProb = deltaMat ? 1.0f : rr_probability(sc, pathLength); // RussianRoulette: delta materials are never terminated
+			const float scatProb = deltaOnly ? 1.0f : rr_probability(sc, pathLength); // RussianRoulette: delta materials are never terminated
 			bool cont			 = !(scatProb <= PR_EPS);
 			if (cont && scatProb < 1.0f) {
 				const float rp = rng_float(rnd);
@@ -1993,16 +2111,37 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 				V3 Lt;
 				Blob integral_weight, pdf_s;
 				bool heroCollapsing = false;
-				bool sampleDelta	= deltaMat;
-				if (roughMat && IMG) {
+				float mix_weight = 1.0f, mix_pdf = 1.0f;
+				bool child_rough = false;
+				if (comb) {
+					// BlendMaterial::sample (blend.cpp:104-122), AddMaterial::sample (add.cpp:92-110): ONE number picks the child, which then
+					// samples as if the vertex had hit it; blend scales its integral weight AND its pdf by the selection probability
+					// (the weight is not divided by it), add halves the pdf only
+					const bool add	  = mat.kind == PRGPU_MAT_ADD;
+					const float f	  = fminf(1.0f, fmaxf(0.0f, mat.roughness_x));
+					const bool second = !(rng_float(rnd) < (add ? 0.5f : 1 - f));
+					mix_pdf			  = add ? 0.5f : (second ? f : 1 - f);
+					mix_weight		  = add ? 1.0f : mix_pdf;
+					const uint32_t id = second ? mat.thin : mat.two_sided;
+					mix_child<FEATS>(sc, id, wl, gp.uv, mat, albedo_v, child_rough);
+				}
+				// the material that samples: the vertex's own, or the child just chosen (now in `mat`)
+				const bool sampleDeltaMat = comb ? mix_delta_only(mat.kind) : deltaOnly, sampleRoughMat = comb ? child_rough : roughMat;
+				bool sampleDelta	= sampleDeltaMat;
+				if (sampleRoughMat && IMG) {
 					rough_sample_uv(sc, mat, wl, cie_y_blob, Vt, rnd, Lt, integral_weight, pdf_s, sampleDelta, heroCollapsing, gp.uv);
-				} else if (roughMat) {
+				} else if (sampleRoughMat) {
 					rough_sample(sc, mat, wl, cie_y_blob, Vt, rnd, Lt, integral_weight, pdf_s, sampleDelta, heroCollapsing);
 				} else if ((FEATS & FEAT_DELTA_MATERIALS) && mat.kind == PRGPU_MAT_MIRROR) {
 					// MirrorMaterial::sample (mirror.cpp:51-60)
 					pdf_s			= blob(1);
 					integral_weight = albedo_v;
 					Lt				= v3(-Vt.x, -Vt.y, Vt.z);
+				} else if (MIX && mat.kind == PRGPU_MAT_NULL) {
+					// NullMaterial::sample (null.cpp:45-55): the ray goes on as it came, no random number
+					pdf_s			= blob(1);
+					integral_weight = blob(1);
+					Lt				= -Vt;
 				} else if ((FEATS & FEAT_DELTA_MATERIALS) && mat.kind == PRGPU_MAT_CONDUCTOR) {
 					// ConductorMaterial::sample (conductor.cpp:54-71): mirror, per-wavelength Fresnel term, no random number
 					pdf_s		   = blob(1);
@@ -2013,7 +2152,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 					integral_weight = fresnel * albedo_v;
 					Lt				= v3(-Vt.x, -Vt.y, Vt.z);
 					heroCollapsing	= sc.spectra[mat.ior].kind == PRGPU_SPEC_SELLMEIER || sc.spectra[mat.k].kind == PRGPU_SPEC_SELLMEIER;
-				} else if (deltaMat) {
+				} else if (sampleDeltaMat) {
 					// DielectricMaterial::sample (dielectric.cpp:60-114), camera rays
 					pdf_s		  = blob(1);
 					const Blob n2 = spectrum_eval<IMG>(sc, mat.ior, wl, gp.uv);
@@ -2035,6 +2174,12 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 						}
 					}
 					heroCollapsing = sc.spectra[mat.ior].kind == PRGPU_SPEC_SELLMEIER; // isDelta && isSpectralVarying (MaterialData.h:22)
+				} else if (MIX && mat.kind == PRGPU_MAT_OREN_NAYAR) {
+					// OrenNayarMaterial::sample (orennayar.cpp:69-80): cosine hemisphere around +N, NOT flipped to the viewer's side
+					const float s1 = rng_float(rnd), s2 = rng_float(rnd);
+					Lt				= cos_hemi(s1, s2);
+					integral_weight = oren_nayar_calc(albedo_v, mat.roughness_x, Vt, Lt, fmaxf(0.0f, Lt.z));
+					pdf_s			= blob(Lt.z * PR_INV_PI_F);
 				} else if (!mat.two_sided && Vt.z < 0.0f) {
 					Lt				= v3(0, 0, 0);
 					integral_weight = blob(0);
@@ -2046,6 +2191,10 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 					pdf_s			= blob(Lt.z * PR_INV_PI_F);
 					if (signbit(Vt.z) != signbit(Lt.z))
 						Lt = -Lt;
+				}
+				if (comb) {
+					integral_weight = integral_weight * mix_weight;
+					pdf_s			= pdf_s * mix_pdf;
 				}
 				const V3 L = normalized(from_tangent_space(N, gp.Nx, gp.Ny, Lt));
 				if (with_lpe)

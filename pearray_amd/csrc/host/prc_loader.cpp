@@ -1233,12 +1233,51 @@ struct Loader {
 			m.kind		   = PRGPU_MAT_MIRROR;
 			m.albedo	   = spectral_param(g, { "specularity" }, 1.0f);
 			m.transmission = PRGPU_INVALID_ID;
+		} else if (type == "orennayar" || type == "oren" || type == "rough") { // orennayar.cpp:99-111; create() reads `albedo` only, whatever its specification lists
+			m.kind	 = PRGPU_MAT_OREN_NAYAR;
+			m.albedo = spectral_param(g, { "albedo" }, 1.0f);
+			if (const Value* v = g.get("roughness")) {
+				if (!v->is_number())
+					fail(PRGPU_EUNSUPPORTED, where(g) + ": :roughness must be a number (textured roughness is not supported)");
+				m.roughness_x = (float)v->number();
+			} else {
+				m.roughness_x = 0.5f;
+			}
+		} else if (type == "null") { // null.cpp:68-79: no parameters
+			m.kind	 = PRGPU_MAT_NULL;
+			m.albedo = spectral_param(g, {}, 1.0f);
+		} else if (type == "blend" || type == "mix" || type == "add") { // blend.cpp:144-180, add.cpp:130-165
+			m.kind	 = type == "add" ? PRGPU_MAT_ADD : PRGPU_MAT_BLEND;
+			m.albedo = spectral_param(g, {}, 1.0f);
+			// SceneLoadContext::lookupMaterial: the children are materials declared EARLIER in the file
+			auto child = [&](const char* key) -> uint32_t {
+				const Value* v		  = g.get(key);
+				const std::string ref = v && v->type == Value::STRING ? v->s : std::string();
+				const auto it		  = material_ids.find(ref);
+				if (it == material_ids.end())
+					fail(PRGPU_EINVAL, where(g) + ": material '" + name + "' refers to unknown material '" + ref + "' (:" + key + " names a material declared earlier)");
+				const uint32_t kind = out.materials[it->second].kind;
+				if (kind == PRGPU_MAT_BLEND || kind == PRGPU_MAT_ADD)
+					fail(PRGPU_EUNSUPPORTED, where(g) + ": material '" + name + "': a blend or add material ('" + ref + "') as :" + key + " is not supported");
+				return it->second;
+			};
+			m.two_sided = child("material1");
+			m.thin		= child("material2");
+			if (m.kind == PRGPU_MAT_BLEND) {
+				if (const Value* v = g.get("factor")) {
+					if (!v->is_number())
+						fail(PRGPU_EUNSUPPORTED, where(g) + ": :factor must be a number (a textured factor is not supported)");
+					m.roughness_x = (float)v->number(); // kept as given: clamped to [0, 1] where it is evaluated (blend.cpp:54,109)
+				} else {
+					m.roughness_x = 0.5f;
+				}
+			}
 		} else if (type == "diffuse" || type == "lambert") {
 			m.kind		= PRGPU_MAT_LAMBERT;
 			m.albedo	= spectral_param(g, { "albedo", "base", "diffuse" }, 1.0f);
 			m.two_sided = get_bool(g, "two_sided", true) ? 1 : 0;
 		} else {
-			fail(PRGPU_EUNSUPPORTED, where(g) + ": material type '" + type + "' is not supported (diffuse/lambert, glass/dielectric, conductor/metal, their rough variants and principled are)");
+			fail(PRGPU_EUNSUPPORTED, where(g) + ": material type '" + type + "' is not supported (diffuse/lambert, orennayar/oren/rough, glass/dielectric, conductor/metal, their rough variants, principled, mirror, null, blend/mix and add are)");
 		}
 		material_ids[name] = (uint32_t)out.materials.size();
 		out.materials.push_back(m);

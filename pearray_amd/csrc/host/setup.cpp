@@ -1122,8 +1122,21 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 	}
 	for (uint32_t i = 0; i < d->n_materials; ++i) {
 		const prgpu_material& m = d->materials[i];
-		if (m.kind > PRGPU_MAT_MIRROR)
+		if (m.kind > PRGPU_MAT_ADD)
 			return bad("unknown material kind", PRGPU_EUNSUPPORTED);
+		if (m.kind == PRGPU_MAT_BLEND || m.kind == PRGPU_MAT_ADD) { // two_sided / thin: the children, roughness_x: the blend factor (include/prgpu.h)
+			const char* what = m.kind == PRGPU_MAT_BLEND ? "blend" : "add";
+			for (uint32_t child : { m.two_sided, m.thin }) {
+				if (child >= i) // (a forward reference, or the material itself: the children are evaluated as they stand, in one pass)
+					return bad((std::string(what) + " material " + std::to_string(i) + ": a child must be a material with a smaller index").c_str(), PRGPU_EUNSUPPORTED);
+				if (d->materials[child].kind == PRGPU_MAT_BLEND || d->materials[child].kind == PRGPU_MAT_ADD)
+					return bad((std::string(what) + " material " + std::to_string(i) + ": a blend or add material as a child is not supported").c_str(), PRGPU_EUNSUPPORTED);
+			}
+			if (m.kind == PRGPU_MAT_BLEND && !std::isfinite(m.roughness_x))
+				return bad(("blend material " + std::to_string(i) + ": the factor must be finite").c_str());
+		}
+		if (m.kind == PRGPU_MAT_OREN_NAYAR && !std::isfinite(m.roughness_x))
+			return bad("oren-nayar roughness must be finite");
 		const bool conductor = m.kind == PRGPU_MAT_CONDUCTOR || m.kind == PRGPU_MAT_ROUGH_CONDUCTOR;
 		const bool glass	 = m.kind == PRGPU_MAT_DIELECTRIC || m.kind == PRGPU_MAT_ROUGH_DIELECTRIC;
 		if (conductor && (m.ior >= d->n_spectra || m.k >= d->n_spectra))
@@ -1162,7 +1175,9 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 			if (E.kind != PRGPU_ENTITY_SPHERE || d->tri_material[E.first_tri] == PRGPU_INVALID_ID)
 				continue;
 			const prgpu_material& m = d->materials[d->tri_material[E.first_tri]];
-			if (textured(m.albedo) || textured(m.ior) || textured(m.k) || textured(m.transmission))
+			auto textured_material	= [&](const prgpu_material& mm) { return textured(mm.albedo) || textured(mm.ior) || textured(mm.k) || textured(mm.transmission); };
+			const bool combinator	= m.kind == PRGPU_MAT_BLEND || m.kind == PRGPU_MAT_ADD; // its children are what the vertex evaluates
+			if (combinator ? (textured_material(d->materials[m.two_sided]) || textured_material(d->materials[m.thin])) : textured_material(m))
 				return bad("textured materials on sphere entities are not supported (their uv needs atan2 / acos)", PRGPU_EUNSUPPORTED);
 		}
 	}

@@ -428,8 +428,13 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 		for (uint32_t i = 0; i < d->n_triangles; ++i) {
 			const uint32_t m = d->tri_material[i];
 			if (m != PRGPU_INVALID_ID) {
-				const uint32_t kind = d->materials[m].kind;
-				cls[i] = (kind == PRGPU_MAT_ROUGH_CONDUCTOR || kind == PRGPU_MAT_ROUGH_DIELECTRIC || kind == PRGPU_MAT_PRINCIPLED) ? 1 : 0;
+				auto rough = [&](uint32_t id) {
+					const uint32_t kind = d->materials[id].kind;
+					return kind == PRGPU_MAT_ROUGH_CONDUCTOR || kind == PRGPU_MAT_ROUGH_DIELECTRIC || kind == PRGPU_MAT_PRINCIPLED;
+				};
+				const prgpu_material& M = d->materials[m];
+				const bool combinator	= M.kind == PRGPU_MAT_BLEND || M.kind == PRGPU_MAT_ADD; // a vertex on it runs the closures of its children
+				cls[i] = (combinator ? (rough(M.two_sided) || rough(M.thin)) : rough(m)) ? 1 : 0;
 			}
 		}
 		UP(sc.tri_class, cls);
@@ -557,6 +562,8 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 		const uint32_t kind = d->materials[i].kind;
 		if (kind == PRGPU_MAT_DIELECTRIC || kind == PRGPU_MAT_CONDUCTOR || kind == PRGPU_MAT_MIRROR)
 			sc.features |= prd::FEAT_DELTA_MATERIALS;
+		else if (kind == PRGPU_MAT_OREN_NAYAR || kind == PRGPU_MAT_NULL || kind == PRGPU_MAT_BLEND || kind == PRGPU_MAT_ADD) // the top variant only (children set their own bits)
+			sc.features |= prd::FEAT_MIX_MATERIALS;
 		else if (kind != PRGPU_MAT_LAMBERT) // rough closures fall back to the smooth ones below roughness 1e-3
 			sc.features |= prd::FEAT_DELTA_MATERIALS | prd::FEAT_ROUGH_MATERIALS;
 	}
@@ -568,7 +575,7 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 		else if (d->entities[e].kind == PRGPU_ENTITY_DISK)
 			sc.features |= prd::FEAT_DISKS;
 	// measurement aid: run a scene with a larger kernel variant than it needs (same results; LPE and quadrics need data the scene does not have)
-	sc.features |= read_knobs().force_features & prd::FEAT_ALL & ~(prd::FEAT_LPE | prd::FEAT_QUADRICS | prd::FEAT_DISKS | prd::FEAT_IMAGES);
+	sc.features |= read_knobs().force_features & prd::FEAT_ALL & ~(prd::FEAT_LPE | prd::FEAT_QUADRICS | prd::FEAT_DISKS | prd::FEAT_IMAGES | prd::FEAT_MIX_MATERIALS);
 	sc.scene_radius	 = t.scene_radius;
 	sc.wl_cdf_size	 = (uint32_t)t.wl_cdf.size();
 	sc.wl_u_offset	 = t.wl_u_offset;
@@ -2008,6 +2015,7 @@ int prgpu_pipeline_info_get(prgpu_scene* s, prgpu_pipeline_info* out)
 	out->bvh_cost_6_wide = s->bvh_cost6;
 	out->bvh_stack_bound = s->bvh_stack_bound;
 	out->bvh_top		 = s->bvh_top;
+	out->variant		 = (uint32_t)prd::PATH_VARIANTS[prd::path_variant(s->sc.features)].id;
 	return PRGPU_OK;
 }
 

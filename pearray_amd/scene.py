@@ -229,6 +229,34 @@ class SceneBuilder:
         self.materials.append(m)
         return len(self.materials) - 1
 
+    def oren_nayar(self, albedo, roughness=0.5):
+        """(material :type 'orennayar'|'oren'|'rough'), orennayar.cpp:99-111: one sided, no `two_sided`"""
+        self.materials.append(abi.Material(abi.MAT_OREN_NAYAR, albedo, 0, 0, 0, 0, 0, 0, float(roughness), 0.0))
+        return len(self.materials) - 1
+
+    def null(self):
+        """(material :type 'null'), null.cpp: passes every ray on unchanged (delta-only)"""
+        self.materials.append(abi.Material(abi.MAT_NULL, self.spectrum_const(1.0), 0, 0, 0, 0, 0))
+        return len(self.materials) - 1
+
+    def _combinator(self, kind, m1, m2, factor):
+        for m in (m1, m2):
+            if not 0 <= m < len(self.materials):
+                raise ValueError("blend / add: child %r is not a material added before" % (m,))
+            if self.materials[m].kind in (abi.MAT_BLEND, abi.MAT_ADD):
+                raise ValueError("blend / add: a blend or add material as a child is not supported")
+        self.materials.append(abi.Material(kind, self.spectrum_const(1.0), m1, 0, 0, m2, 0, 0, float(factor), 0.0))
+        return len(self.materials) - 1
+
+    def blend(self, m1, m2, factor=0.5):
+        """(material :type 'blend'|'mix' :material1 :material2 :factor), blend.cpp:144-180: `factor` 0 is m1 alone; kept as given and
+        clamped to [0, 1] where it is evaluated"""
+        return self._combinator(abi.MAT_BLEND, m1, m2, factor)
+
+    def add(self, m1, m2):
+        """(material :type 'add' :material1 :material2), add.cpp:130-165"""
+        return self._combinator(abi.MAT_ADD, m1, m2, 0.0)
+
     def diffuse_emission(self, radiance):
         self.emissions.append(abi.Emission(abi.EMS_DIFFUSE, radiance))
         return len(self.emissions) - 1
