@@ -51,7 +51,8 @@ extern "C" {
 #define PRGPU_API_VERSION 8 /* layout version of the structs below (prgpu_scene_desc::api_version); entry points added since keep it: round 5 added
                                prgpu_pipeline_info_get, prgpu_comm_query, prgpu_reduced_planes; PRGPU_ENTITY_DISK and PRGPU_SPEC_IMAGE are new enumerators, no field moved;
                                prgpu_image_load came with the latter; PRGPU_MAT_OREN_NAYAR, PRGPU_MAT_NULL, PRGPU_MAT_BLEND and PRGPU_MAT_ADD are new
-                               enumerators that reuse fields of prgpu_material, no field moved */
+                               enumerators that reuse fields of prgpu_material, no field moved; PRGPU_SPEC_ADD .. PRGPU_SPEC_PEAK are new enumerators
+                               that reuse lhs / rhs / p of prgpu_spectrum, no field moved */
 #define PRGPU_INVALID_ID 0xFFFFFFFFu /* PR_INVALID_ID, src/base/config/Constants.inl:6 */
 
 enum {
@@ -89,9 +90,35 @@ enum {
  *                      SPECTRA ((s00 (1-fx) + s10 fx)(1-fy) + (s01 (1-fx) + s11 fx) fy) -- the reference blends RGB, then upsamples.
  *                      Placement as CHECKER: a material parameter or an operand of CHECKER; not inside MUL, not an emission, not on
  *                      infinite lights, not on sphere entities.
- * MUL operands must have a smaller index than the node itself (topological order); so must CHECKER operands. */
+ *   ADD SUB DIV MAX MIN BURN SCREEN DODGE OVERLAY SOFTLIGHT HARDLIGHT
+ *                      the binary nodes of SpectralMathNode.cpp:73-96 (`sadd` `ssub` `sdiv` `smax` `smin` `sburn` `sscreen` `sdodge` `soverlay`
+ *                      `ssoftlight` `shardlight`), per wavelength in fp32 with a = lhs, b = rhs: a+b, a-b, a/b, max, min,
+ *                      1-(1-a)/(b+1), 1-(1-a)(1-b), a/((1-b)+1), a(a+2b(1-a)), ((1-a)b + screen(a,b))a, b <= 0.5 ? 2ba : 1-(1-2(b-0.5))(1-a).
+ *   NEG ABS            the unary nodes (`sneg`, `sabs`, :67-71): operand lhs; rhs is PRGPU_INVALID_ID.
+ *   BLEND              ConstBlendSpectralMath (`sblend factor op1 op2`, :115-149): lhs (1-f) + rhs f, f = p[0], not clamped.
+ *   BRIGHTNESS_CONTRAST ConstBCSpectralMath (`sbrightnesscontrast color brightness contrast`, :188-228): max(0, (1+c) lhs + (b - c/2)),
+ *                      b = p[0], c = p[1]; rhs is PRGPU_INVALID_ID.
+ *   BLACKBODY          ConstBlackbodyNode (`blackbody`, BlackbodyNode.cpp, core/spectral/Blackbody.h): Planck's law in double,
+ *                      float(2hc^2/l^5 / expm1(hc/(kb l T))) p[1], l = double(wavelength 1e-9f); p[0] = T [K] > 0, p[1] = the peak
+ *                      normalisation 1 / blackbody(2.897771955e6f / T, T) in float (the reference always normalises a constant T).
+ *   PEAK               TrianglePeakNodeConst (`triangle_peak`, `peak`): max(0, 1 - |wavelength - p[0]| / p[1]), p[1] = radius > 0.
+ *                      BLACKBODY and PEAK are NodeFlag::SpectralVarying, as SELLMEIER is; a math node is when an operand is.
+ * MUL operands must have a smaller index than the node itself (topological order); so must CHECKER operands and those of the nodes above.
+ * A MUL of two leaves (CONST .. TABLE, SELLMEIER) is evaluated in place.  Every other math node, BLACKBODY, PEAK, a MUL with such an operand
+ * -- and a MUL over a SELLMEIER leaf, which is spectral varying -- is an EXPRESSION: where a material, an emission, an infinite light or a
+ * CHECKER operand names one, the scene compiles that root to a postfix program for a stack machine (the deeper operand first).  Two bounds,
+ * beyond which prgpu_scene_create answers PRGPU_EUNSUPPORTED: the operand stack a root needs (leaf 1; unary: its operand's; binary: the larger
+ * of its operands', one more when they are equal) is at most PRGPU_EXPR_MAX_STACK, and a root's program (one word per node reached, a shared
+ * node counted once per path to it) has at most PRGPU_EXPR_MAX_PROGRAM words.  No CHECKER or IMAGE below a math node.  An expression may
+ * stand wherever MUL may (material parameters, emissions, infinite lights, CHECKER operands). */
 enum { PRGPU_SPEC_CONST = 0, PRGPU_SPEC_PARAMETRIC = 1, PRGPU_SPEC_PARAMETRIC_SCALED = 2,
-       PRGPU_SPEC_TABLE = 3, PRGPU_SPEC_MUL = 4, PRGPU_SPEC_SELLMEIER = 5, PRGPU_SPEC_CHECKER = 6, PRGPU_SPEC_IMAGE = 7 };
+       PRGPU_SPEC_TABLE = 3, PRGPU_SPEC_MUL = 4, PRGPU_SPEC_SELLMEIER = 5, PRGPU_SPEC_CHECKER = 6, PRGPU_SPEC_IMAGE = 7,
+       PRGPU_SPEC_ADD = 8, PRGPU_SPEC_SUB = 9, PRGPU_SPEC_DIV = 10, PRGPU_SPEC_NEG = 11, PRGPU_SPEC_ABS = 12, PRGPU_SPEC_MAX = 13,
+       PRGPU_SPEC_MIN = 14, PRGPU_SPEC_BURN = 15, PRGPU_SPEC_SCREEN = 16, PRGPU_SPEC_DODGE = 17, PRGPU_SPEC_OVERLAY = 18,
+       PRGPU_SPEC_SOFTLIGHT = 19, PRGPU_SPEC_HARDLIGHT = 20, PRGPU_SPEC_BLEND = 21, PRGPU_SPEC_BRIGHTNESS_CONTRAST = 22,
+       PRGPU_SPEC_BLACKBODY = 23, PRGPU_SPEC_PEAK = 24 };
+#define PRGPU_EXPR_MAX_STACK   4  /* operand-stack entries of the device evaluator: four blobs held in registers */
+#define PRGPU_EXPR_MAX_PROGRAM 64 /* words of one root's program */
 
 typedef struct prgpu_spectrum {
 	uint32_t kind;
@@ -100,7 +127,7 @@ typedef struct prgpu_spectrum {
 	uint32_t table_count;   /* TABLE: number of samples (>= 2); IMAGE: 4 (W*H + 1) */
 	float    wl_start;      /* TABLE: wavelength of first sample [nm] */
 	float    wl_end;        /* TABLE: wavelength of last sample [nm] */
-	uint32_t lhs, rhs;      /* MUL: operand node indices; CHECKER: op1 (odd cells), op2 (even cells); IMAGE: width, height */
+	uint32_t lhs, rhs;      /* MUL and the other math nodes: operand node indices (unary: rhs = PRGPU_INVALID_ID); CHECKER: op1 (odd cells), op2 (even cells); IMAGE: width, height */
 } prgpu_spectrum;
 
 /* LAMBERT     src/plugins/main/materials/lambert.cpp

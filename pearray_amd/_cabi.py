@@ -14,6 +14,13 @@ INVALID_ID = 0xFFFFFFFF
 COMM_ID_BYTES = 128
 
 SPEC_CONST, SPEC_PARAMETRIC, SPEC_PARAMETRIC_SCALED, SPEC_TABLE, SPEC_MUL, SPEC_SELLMEIER, SPEC_CHECKER, SPEC_IMAGE = range(8)
+# the spectral expression nodes (include/prgpu.h): the reference's node names, in the order of their enumerators
+(SPEC_ADD, SPEC_SUB, SPEC_DIV, SPEC_NEG, SPEC_ABS, SPEC_MAX, SPEC_MIN, SPEC_BURN, SPEC_SCREEN, SPEC_DODGE, SPEC_OVERLAY, SPEC_SOFTLIGHT,
+ SPEC_HARDLIGHT, SPEC_BLEND, SPEC_BRIGHTNESS_CONTRAST, SPEC_BLACKBODY, SPEC_PEAK) = range(8, 25)
+SPEC_OPS = {"smul": SPEC_MUL, "sadd": SPEC_ADD, "ssub": SPEC_SUB, "sdiv": SPEC_DIV, "sneg": SPEC_NEG, "sabs": SPEC_ABS, "smax": SPEC_MAX,
+            "smin": SPEC_MIN, "sburn": SPEC_BURN, "sscreen": SPEC_SCREEN, "sdodge": SPEC_DODGE, "soverlay": SPEC_OVERLAY,
+            "ssoftlight": SPEC_SOFTLIGHT, "shardlight": SPEC_HARDLIGHT, "sblend": SPEC_BLEND, "sbrightnesscontrast": SPEC_BRIGHTNESS_CONTRAST}
+EXPR_MAX_STACK, EXPR_MAX_PROGRAM = 4, 64
 MAT_LAMBERT, MAT_DIELECTRIC, MAT_CONDUCTOR, MAT_ROUGH_CONDUCTOR, MAT_ROUGH_DIELECTRIC, MAT_PRINCIPLED, MAT_MIRROR = 0, 1, 2, 3, 4, 5, 6
 MAT_OREN_NAYAR, MAT_NULL, MAT_BLEND, MAT_ADD = 7, 8, 9, 10   # BLEND / ADD: two_sided, thin = the two children's material indices, roughness_x = the blend factor
 MATF_ANISOTROPIC, MATF_NO_VNDF, MATF_HAS_TRANSMISSION = 1, 2, 4

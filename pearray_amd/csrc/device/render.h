@@ -69,13 +69,15 @@ void launch_path_persistent(const DevScene& sc, const PathState& ps, const uint3
 // closures dominate such scenes, 156 vs 154 Msamples/s.  Light path expressions are a row of their own because their state tracking costs
 // the all-features kernel 7 % (C5 135 -> 125 Msamples/s); quadric and disk entities, image textures (FEAT_IMAGES) and the Oren-Nayar / null / blend / add
 // materials (FEAT_MIX_MATERIALS) ride in that top row (what a disk or an image scene pays for the expression hooks there has not been measured).
+// Spectral expression roots (FEAT_EXPR) ride there too, in exactly the rows that have FEAT_IMAGES: the closures'
+// _uv forms (rough_closures.inl) serve both.
 // A translation unit of render.hip takes its row by -DPR_VARIANT=<id>.  Adding a variant takes exactly two edits: a row here, and its id in
 // the Makefile's VARIANTS list.
 struct PathVariant {
 	int id;			   // PR_VARIANT of its translation units; bit id - 1 of PR_PL_VARIANTS
 	uint32_t features; // FEAT_* bits the kernel is compiled with
 };
-constexpr uint32_t FEAT_NO_LPE = FEAT_ALL & ~(FEAT_LPE | FEAT_QUADRICS | FEAT_DISKS | FEAT_IMAGES | FEAT_MIX_MATERIALS), FEAT_NO_ROUGH = FEAT_NO_LPE & ~FEAT_ROUGH_MATERIALS;
+constexpr uint32_t FEAT_NO_LPE = FEAT_ALL & ~(FEAT_LPE | FEAT_QUADRICS | FEAT_DISKS | FEAT_IMAGES | FEAT_MIX_MATERIALS | FEAT_EXPR), FEAT_NO_ROUGH = FEAT_NO_LPE & ~FEAT_ROUGH_MATERIALS;
 constexpr PathVariant PATH_VARIANTS[] = { { 1, 0u }, { 2, FEAT_DELTA_MATERIALS }, { 3, FEAT_NO_ROUGH }, { 4, FEAT_NO_LPE }, { 5, FEAT_ALL } };
 constexpr int N_PATH_VARIANTS		  = int(sizeof(PATH_VARIANTS) / sizeof(PATH_VARIANTS[0]));
 // index of the scene's row
@@ -102,6 +104,14 @@ constexpr bool path_variants_nested()
 	return true;
 }
 static_assert(PATH_VARIANTS[N_PATH_VARIANTS - 1].features == FEAT_ALL, "the last variant must cover every scene");
+constexpr bool expr_rides_with_images()
+{
+	for (int i = 0; i < N_PATH_VARIANTS; ++i)
+		if (((PATH_VARIANTS[i].features & FEAT_IMAGES) != 0u) != ((PATH_VARIANTS[i].features & FEAT_EXPR) != 0u))
+			return false;
+	return true;
+}
+static_assert(expr_rides_with_images(), "FEAT_EXPR and FEAT_IMAGES must sit in the same rows: the closures' _uv forms serve both");
 static_assert(path_variants_nested(), "each variant's mask must be contained in the next one's: then the first covering row is the smallest covering one");
 // The throughput organisation compiles every variant in these forms (its sub-units, -DPR_SUB=<index>): for 3 waves per SIMD with four-
 // or six-wide inner records, or for 2 waves per SIMD (one kernel for both widths), each plain and instrumented (COUNT).

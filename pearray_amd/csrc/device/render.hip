@@ -535,29 +535,140 @@ __device__ __forceinline__ Blob spectrum_leaf(const DevScene& sc, const prgpu_sp
 	default: return blob(0);
 	}
 }
-// FloatSpectralNode::eval for the flattened network (MUL operands are leaves; validated at scene creation)
-template <bool IMG = false>
+// ---- spectral expressions (FEAT_EXPR builds only) --------------------------------------------------------------
+// An expression root's record on the device carries its postfix program: table_count words at word table_offset of DevScene::tables (the
+// scene compiles them, host/setup.cpp compile_expressions), wl_start != 0 when the expression is NodeFlag::SpectralVarying.  A word is a
+// node index (EXPR_NODE_MASK) and EXPR_SWAP when the compile emitted the node's right operand first (the deeper operand goes first, so
+// that a chain needs two stack entries).
+constexpr uint32_t EXPR_SWAP = 0x80000000u, EXPR_NODE_MASK = 0x00FFFFFFu;
+__device__ __forceinline__ bool expr_is_program(const prgpu_spectrum& n) { return (n.kind == PRGPU_SPEC_MUL || n.kind > PRGPU_SPEC_IMAGE) && n.table_count != 0u; }
+// NodeFlag::SpectralVarying of a node: a delta material whose index / k has it collapses the path to its hero wavelength
+template <bool EXPR>
+__device__ __forceinline__ bool spectrum_varying(const prgpu_spectrum& n)
+{
+	return n.kind == PRGPU_SPEC_SELLMEIER || (EXPR && expr_is_program(n) && n.wl_start != 0.0f);
+}
+// blackbody (core/spectral/Blackbody.h:11-28): Planck's law in double, cast to float, times the node's float peak normalisation
+constexpr double PR_LIGHT_C = 299792458.0, PR_PLANCK_H = 6.62607004081e-34, PR_BOLTZMANN_KB = 1.3806485279e-23; // base/math/SIMathConstants.h:23,37,58
+__device__ __forceinline__ float expr_blackbody(float lambda_nm, float temp_kelvin)
+{
+	const double lambda	 = (double)(lambda_nm * 1e-9f);
+	const double temp	 = (double)temp_kelvin;
+	const double c1		 = 2 * PR_PLANCK_H * PR_LIGHT_C * PR_LIGHT_C;
+	const double c2		 = PR_PLANCK_H * PR_LIGHT_C / PR_BOLTZMANN_KB;
+	const double lambda5 = lambda * (lambda * lambda) * (lambda * lambda);
+	const double f		 = c2 / (lambda * temp);
+	return (float)((c1 / lambda5) / expm1(f));
+}
+// the two leaves only expressions have
+__device__ __forceinline__ Blob expr_leaf(const DevScene& sc, const prgpu_spectrum& n, const Blob& wl)
+{
+	Blob b;
+	if (n.kind == PRGPU_SPEC_BLACKBODY) {
+		for (int k = 0; k < 4; ++k)
+			b.v[k] = expr_blackbody(wl.v[k], n.p[0]) * n.p[1];
+		return b;
+	}
+	if (n.kind == PRGPU_SPEC_PEAK) { // evalTriangle (TrianglePeakNode.cpp:8-11)
+		for (int k = 0; k < 4; ++k)
+			b.v[k] = fmaxf(0.0f, 1.0f - fabsf(wl.v[k] - n.p[0]) / n.p[1]);
+		return b;
+	}
+	return spectrum_leaf(sc, n, wl);
+}
+// one lane of a unary / binary / parametrised operator (SpectralMathNode.cpp:67-96,128,188-194), in the reference's operand order
+__device__ __forceinline__ float expr_op(uint32_t kind, float a, float b, float p0, float p1)
+{
+	switch (kind) {
+	case PRGPU_SPEC_MUL: return a * b;
+	case PRGPU_SPEC_ADD: return a + b;
+	case PRGPU_SPEC_SUB: return a - b;
+	case PRGPU_SPEC_DIV: return a / b;
+	case PRGPU_SPEC_NEG: return -a;
+	case PRGPU_SPEC_ABS: return fabsf(a);
+	case PRGPU_SPEC_MAX: return fmaxf(a, b);
+	case PRGPU_SPEC_MIN: return fminf(a, b);
+	case PRGPU_SPEC_BURN: return 1 - (1 - a) / (b + 1);
+	case PRGPU_SPEC_SCREEN: return 1 - (1 - a) * (1 - b);
+	case PRGPU_SPEC_DODGE: return a / ((1 - b) + 1);
+	case PRGPU_SPEC_OVERLAY: return a * (a + 2 * b * (1 - a));
+	case PRGPU_SPEC_SOFTLIGHT: {
+		const float r = 1 - (1 - a) * (1 - b);
+		return ((1 - a) * b + r) * a;
+	}
+	case PRGPU_SPEC_HARDLIGHT: {
+		const float k1 = 1 - (1 - 2 * (b - 0.5f)) * (1 - a);
+		const float k2 = 2 * b * a;
+		return b <= 0.5f ? k2 : k1;
+	}
+	case PRGPU_SPEC_BLEND: return a * (1 - p0) + b * p0;
+	case PRGPU_SPEC_BRIGHTNESS_CONTRAST: return fmaxf((1.0f + p1) * a + (p0 - p1 * 0.5f), 0.0f);
+	default: return 0.0f;
+	}
+}
+// The stack machine over four-wavelength blobs.  The operand stack is four NAMED blobs that shift on a push and a pop (s0 is the top): no
+// runtime-indexed array, so nothing goes to scratch.  The scene bounds the depth (PRGPU_EXPR_MAX_STACK = 4) and the program's length.
+// (static and out of line: one copy per unit that calls it, none in the units without FEAT_EXPR)
+static __device__ __attribute__((noinline)) Blob expr_eval(const DevScene& sc, const prgpu_spectrum& root, const Blob& wl)
+{
+	static_assert(PRGPU_EXPR_MAX_STACK == 4, "expr_eval keeps exactly four stack entries in registers");
+	const uint32_t* __restrict__ prog = reinterpret_cast<const uint32_t*>(sc.tables) + root.table_offset;
+	Blob s0 = blob(0), s1 = blob(0), s2 = blob(0), s3 = blob(0);
+#pragma unroll 1
+	for (uint32_t i = 0; i < root.table_count; ++i) {
+		const uint32_t word		= prog[i];
+		const prgpu_spectrum& n = sc.spectra[word & EXPR_NODE_MASK];
+		const uint32_t kind		= n.kind;
+		if (kind == PRGPU_SPEC_MUL || (kind > PRGPU_SPEC_IMAGE && kind < PRGPU_SPEC_BLACKBODY)) {
+			const bool unary = kind == PRGPU_SPEC_NEG || kind == PRGPU_SPEC_ABS || kind == PRGPU_SPEC_BRIGHTNESS_CONTRAST;
+			const bool swap	 = (word & EXPR_SWAP) != 0u;
+			const Blob a = unary ? s0 : (swap ? s0 : s1), b = swap ? s1 : s0;
+			Blob r;
+			for (int k = 0; k < 4; ++k)
+				r.v[k] = expr_op(kind, a.v[k], b.v[k], n.p[0], n.p[1]);
+			s0 = r;
+			if (!unary) {
+				s1 = s2;
+				s2 = s3;
+			}
+		} else {
+			s3 = s2;
+			s2 = s1;
+			s1 = s0;
+			s0 = expr_leaf(sc, n, wl);
+		}
+	}
+	return s0;
+}
+// FloatSpectralNode::eval for the flattened network (MUL operands are leaves, or the node is an expression root; validated at scene creation)
+// EXPR: the FEAT_EXPR builds, whose scenes may hold expression roots
+template <bool IMG = false, bool EXPR = false>
 __device__ __forceinline__ Blob spectrum_eval(const DevScene& sc, uint32_t id, const Blob& wl, const float* uv = nullptr)
 {
 	const prgpu_spectrum& n = sc.spectra[id];
+	if (EXPR && expr_is_program(n))
+		return expr_eval(sc, n, wl);
 	if (n.kind == PRGPU_SPEC_MUL) // (no image inside a product: validated at scene creation)
 		return spectrum_leaf(sc, sc.spectra[n.lhs], wl) * spectrum_leaf(sc, sc.spectra[n.rhs], wl);
 	return spectrum_leaf<IMG>(sc, n, wl, uv);
 }
 
 // the same for a node (and the operands of a product node) already in registers: DevLight / DevMaterial carry copies
+template <bool EXPR = false>
 __device__ __forceinline__ Blob spectrum_eval_copy(const DevScene& sc, const prgpu_spectrum& n, const prgpu_spectrum& lhs, const prgpu_spectrum& rhs, const Blob& wl)
 {
+	if (EXPR && expr_is_program(n))
+		return expr_eval(sc, n, wl);
 	if (n.kind == PRGPU_SPEC_MUL)
 		return spectrum_leaf(sc, lhs, wl) * spectrum_leaf(sc, rhs, wl);
 	return spectrum_leaf(sc, n, wl);
 }
 // albedo / specularity of a material: the copy next to the material unless a texture resolved the parameter to another node
-template <bool IMG = false>
+template <bool IMG = false, bool EXPR = false>
 __device__ __forceinline__ Blob albedo_eval(const DevScene& sc, const prgpu_material& mat, const prgpu_spectrum& copy, uint32_t copy_id, const Blob& wl, const float* uv = nullptr)
 {
-	if (mat.albedo != copy_id || copy.kind == PRGPU_SPEC_MUL)
-		return spectrum_eval<IMG>(sc, mat.albedo, wl, uv);
+	if (mat.albedo != copy_id || copy.kind == PRGPU_SPEC_MUL || (EXPR && copy.kind > PRGPU_SPEC_IMAGE))
+		return spectrum_eval<IMG, EXPR>(sc, mat.albedo, wl, uv);
 	return spectrum_leaf<IMG>(sc, copy, wl, uv);
 }
 // CheckerboardNode::eval (CheckerboardNode.cpp:26-48): a textured material parameter resolves to the plain node of the uv cell -- which
@@ -1469,7 +1580,7 @@ __device__ __forceinline__ void mix_child(const DevScene& sc, uint32_t id, const
 		m.transmission = resolve_texture(sc, m.transmission, uv);
 	}
 	rough  = (FEATS & FEAT_ROUGH_MATERIALS) && (m.kind == PRGPU_MAT_ROUGH_CONDUCTOR || m.kind == PRGPU_MAT_ROUGH_DIELECTRIC || m.kind == PRGPU_MAT_PRINCIPLED);
-	albedo = rough ? blob(0) : albedo_eval<(FEATS & FEAT_IMAGES) != 0u>(sc, m, dm.albedo, dm.m.albedo, wl, uv);
+	albedo = rough ? blob(0) : albedo_eval<(FEATS & FEAT_IMAGES) != 0u, (FEATS & FEAT_EXPR) != 0u>(sc, m, dm.albedo, dm.m.albedo, wl, uv);
 }
 // IMaterial::eval of the vertex's material for next event estimation in the FEAT_MIX_MATERIALS builds (the others call material_eval, as
 // before).  Without a combinator this is material_eval.  With one
@@ -1528,6 +1639,7 @@ __device__ __forceinline__ void vertex_eval(const DevScene& sc, const prgpu_mate
 }
 
 // CIESimpleSkyLight::radiance (cie_sky.cpp:108-126) for a world direction; (z + 1.01)^10 by squaring in fp32
+template <bool EXPR = false>
 __device__ __forceinline__ Blob cie_sky_radiance(const DevScene& sc, const DevInfLight& il, const Blob& wl, V3 dir)
 {
 	const V3 tD		  = mat3_mul(il.inv_nm, dir);
@@ -1541,8 +1653,8 @@ __device__ __forceinline__ Blob cie_sky_radiance(const DevScene& sc, const DevIn
 		c1 = (1 + 2.0f * tD.z) / 3.0f;
 		c2 = 0.7777777f;
 	}
-	const Blob zenith = spectrum_eval(sc, il.radiance, wl);
-	const Blob ground = spectrum_eval(sc, il.background != INVALID ? il.background : il.radiance, wl);
+	const Blob zenith = spectrum_eval<false, EXPR>(sc, il.radiance, wl);
+	const Blob ground = spectrum_eval<false, EXPR>(sc, il.background != INVALID ? il.background : il.radiance, wl);
 	const float wz = c1 * a, wg = il.ground_brightness * c2 * b;
 	Blob out;
 	for (int k = 0; k < 4; ++k)
@@ -1553,6 +1665,7 @@ __device__ __forceinline__ Blob cie_sky_radiance(const DevScene& sc, const DevIn
 // background), SkyLight (sky.cpp:51-79), SunLight (sun.cpp:61-77).  Delta lights (DISTANT) are never evaluated.
 // textured ENVIRONMENT light (PRGPU_ENVF_TEXTURED): the `radiance` node times ParametricImageNode::eval (loader/shader/ImageNode.cpp:48-73)
 // at the texel under (u, 1 - v) -- closest-texel interpolation, u periodic, v clamped
+template <bool EXPR = false>
 __device__ __forceinline__ Blob env_image_eval(const DevScene& sc, const DevInfLight& il, const Blob& wl, float u, float v)
 {
 	const uint32_t W = il.az_count, H = il.el_count;
@@ -1562,7 +1675,7 @@ __device__ __forceinline__ Blob env_image_eval(const DevScene& sc, const DevInfL
 	const uint32_t row = min(H - 1u, (uint32_t)(tv * (float)H));
 	const float* c	   = sc.tables + il.table_offset + 3u * (size_t(row) * W + col);
 	const float p[3]   = { c[0], c[1], c[2] };
-	const Blob base	   = spectrum_eval(sc, il.radiance, wl);
+	const Blob base	   = spectrum_eval<false, EXPR>(sc, il.radiance, wl);
 	return blob4(base.v[0] * upsample(p, wl.v[0]), base.v[1] * upsample(p, wl.v[1]), base.v[2] * upsample(p, wl.v[2]), base.v[3] * upsample(p, wl.v[3]));
 }
 // Spherical::uv_from_normal (base/math/Spherical.h:8-26) through the shared fp32 atan2 / acos: u = phi / (2 pi), v = theta / pi
@@ -1583,13 +1696,14 @@ __device__ __forceinline__ float env_jacobian(float v)
 	const float denom = 2 * PR_PI_F * PR_PI_F * s;
 	return denom <= PR_EPS ? 0.0f : 1.0f / denom;
 }
+template <bool EXPR = false> // EXPR: the FEAT_EXPR builds, whose radiance nodes may be expression roots
 __device__ __forceinline__ void inf_light_eval(const DevScene& sc, const DevInfLight& il, V3 dir, const Blob& wl, bool camera_ray, Blob& radiance, float& dir_pdf)
 {
 	if (il.kind == PRGPU_LIGHT_ENVIRONMENT && (il.flags & PRGPU_ENVF_TEXTURED)) { // EnvironmentLight::eval (environment.cpp:53-73)
 		const V3 ld = mat3_mul(il.inv_nm, dir);
 		float u, v;
 		uv_from_direction(ld, u, v);
-		radiance = (camera_ray && il.background != INVALID) ? spectrum_eval(sc, il.background, wl) : env_image_eval(sc, il, wl, u, v);
+		radiance = (camera_ray && il.background != INVALID) ? spectrum_eval<false, EXPR>(sc, il.background, wl) : env_image_eval<EXPR>(sc, il, wl, u, v);
 		if (il.dist_w)
 			dir_pdf = distribution2d_pdf(sc.sky_cdf + il.dist_offset, il.dist_w, il.dist_h, u, v) * env_jacobian(v);
 		else
@@ -1616,27 +1730,28 @@ __device__ __forceinline__ void inf_light_eval(const DevScene& sc, const DevInfL
 			radiance = blob(0);
 			dir_pdf	 = 0.0f;
 		} else {
-			radiance = spectrum_eval(sc, il.radiance, wl);
+			radiance = spectrum_eval<false, EXPR>(sc, il.radiance, wl);
 			dir_pdf	 = il.cone_pdf;
 		}
 		return;
 	}
 	if (il.kind == PRGPU_LIGHT_CIE_SKY) { // cie_sky.cpp:48-53
-		radiance = cie_sky_radiance(sc, il, wl, dir);
+		radiance = cie_sky_radiance<EXPR>(sc, il, wl, dir);
 		dir_pdf	 = fabsf(mat3_mul(il.inv_nm, dir).z) * PR_INV_PI_F;
 		return;
 	}
-	radiance	= spectrum_eval(sc, (camera_ray && il.background != INVALID) ? il.background : il.radiance, wl);
+	radiance	= spectrum_eval<false, EXPR>(sc, (camera_ray && il.background != INVALID) ? il.background : il.radiance, wl);
 	const V3 ld = mat3_mul(il.inv_nm, dir);
 	dir_pdf		= fabsf(ld.z) * PR_INV_PI_F;
 }
 // IInfiniteLight::sampleDir: distant.cpp:58-77, environment.cpp:75-116 (no distribution), sky.cpp:81-98, sun.cpp:79-88
+template <bool EXPR = false>
 __device__ __forceinline__ void inf_light_sample(const DevScene& sc, const DevInfLight& il, float d0, float d1, const Blob& wl, V3& L, float& dir_pdf, Blob& radiance)
 {
 	if (il.kind == PRGPU_LIGHT_DISTANT) {
 		L		 = v3(il.outgoing[0], il.outgoing[1], il.outgoing[2]);
 		dir_pdf	 = 1.0f;
-		radiance = spectrum_eval(sc, il.radiance, wl);
+		radiance = spectrum_eval<false, EXPR>(sc, il.radiance, wl);
 	} else if (il.kind == PRGPU_LIGHT_ENVIRONMENT && (il.flags & PRGPU_ENVF_TEXTURED)) { // EnvironmentLight::sampleDir (environment.cpp:75-101)
 		float u, v;
 		V3 lo;
@@ -1654,7 +1769,7 @@ __device__ __forceinline__ void inf_light_sample(const DevScene& sc, const DevIn
 			dir_pdf = lo.z * PR_INV_PI_F;
 		}
 		L		 = mat3_mul(il.nm, lo);
-		radiance = env_image_eval(sc, il, wl, u, v);
+		radiance = env_image_eval<EXPR>(sc, il, wl, u, v);
 	} else if (il.kind == PRGPU_LIGHT_SKY) {
 		float u, v;
 		distribution2d_sample(sc.sky_cdf + il.dist_offset, il.dist_w, il.dist_h, d0, d1, u, v, dir_pdf);
@@ -1666,12 +1781,12 @@ __device__ __forceinline__ void inf_light_sample(const DevScene& sc, const DevIn
 		const V3 dir = uniform_cone(d0, d1, il.cos_theta);
 		L			 = from_tangent_space(v3(il.outgoing[0], il.outgoing[1], il.outgoing[2]), v3(il.dx[0], il.dx[1], il.dx[2]), v3(il.dy[0], il.dy[1], il.dy[2]), dir);
 		dir_pdf		 = il.cone_pdf;
-		radiance	 = spectrum_eval(sc, il.radiance, wl);
+		radiance	 = spectrum_eval<false, EXPR>(sc, il.radiance, wl);
 	} else {
 		const V3 lo = cos_hemi(d0, d1);
 		dir_pdf		= lo.z * PR_INV_PI_F;
 		L			= mat3_mul(il.nm, lo);
-		radiance	= il.kind == PRGPU_LIGHT_CIE_SKY ? cie_sky_radiance(sc, il, wl, L) : spectrum_eval(sc, il.radiance, wl); // cie_sky.cpp:55-66
+		radiance	= il.kind == PRGPU_LIGHT_CIE_SKY ? cie_sky_radiance<EXPR>(sc, il, wl, L) : spectrum_eval<false, EXPR>(sc, il.radiance, wl); // cie_sky.cpp:55-66
 	}
 }
 
@@ -1732,6 +1847,7 @@ template <uint32_t FEATS>
 __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState& ps, uint32_t slot, BlockStats& bs, bool& alive, bool& want_shadow,
 											 float4& sh_o, float4& sh_d, float4& sh_xyz, const float4* hit_src = nullptr /* the slot's hit when it is not in ps.hit (latency kernel: LDS) */)
 {
+	constexpr bool EXPR		  = (FEATS & FEAT_EXPR) != 0u; // spectral nodes may be expression roots: their evaluation runs the root's program
 	const prgpu_settings& cfg = sc.cfg;
 	const uint32_t pixel = ps.pixel[slot];
 	const size_t entry	 = iter_entry(ps, slot, pixel);
@@ -1782,7 +1898,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 				illuminated = true;
 				Blob radiance;
 				float dir_pdf;
-				inf_light_eval(sc, il, ray_d, wl, true, radiance, dir_pdf);
+				inf_light_eval<EXPR>(sc, il, ray_d, wl, true, radiance, dir_pdf);
 				fb = fragment_value(sc, blob(1), blob(1), grp_imp, radiance, mono, cie, blend, xyz);
 				apply_fragment(ps, pixel, entry, fb, xyz, m_bg);
 			}
@@ -1800,7 +1916,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 					continue;
 				Blob er;
 				float dir_pdf;
-				inf_light_eval(sc, il, ray_d, wl, false, er, dir_pdf);
+				inf_light_eval<EXPR>(sc, il, ray_d, wl, false, er, dir_pdf);
 				const float selProb = sc.light_cdf[sc.n_lights + k + 1] - sc.light_cdf[sc.n_lights + k];
 				const float pdf_S	= dir_pdf * selProb;
 				for (int c = 0; c < 4; ++c)
@@ -1845,7 +1961,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 			const float cosC = -NdotV;
 			if (!(fabsf(cosC) <= PR_EPS)) {
 				const bool behind	= cosC < 0.0f;
-				const Blob radiance = behind ? blob(0) : spectrum_eval(sc, sc.emissions[gp.emission].radiance, wl);
+				const Blob radiance = behind ? blob(0) : spectrum_eval<false, EXPR>(sc, sc.emissions[gp.emission].radiance, wl);
 				float xyz[3];
 				uint32_t fb;
 				if (!cfg.nee || behind || (flags & FLAG_LAST_DELTA)) {
@@ -1898,7 +2014,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 			// albedo / specularity at the path's wavelengths, once: IMaterial::eval and ::sample of a vertex evaluate the same node at
 			// the same wavelengths (lambert.cpp:38,66; mirror / conductor / dielectric sample).  The rough closures fetch their own.
 			constexpr bool IMG	= (FEATS & FEAT_IMAGES) != 0u; // material parameters may be image textures: their evaluation takes the point's uv
-			Blob albedo_v		= roughMat ? blob(0) : albedo_eval<IMG>(sc, mat, dmat.albedo, dmat.m.albedo, wl, gp.uv);
+			Blob albedo_v		= roughMat ? blob(0) : albedo_eval<IMG, EXPR>(sc, mat, dmat.albedo, dmat.m.albedo, wl, gp.uv);
 			if (cfg.nee && !deltaOnly && !hasEmission && (sc.n_lights + ((FEATS & FEAT_INFINITE_LIGHTS) ? sc.n_inf_lights : 0u))) { // direct.cpp:100-101
 				// ---- handleNEE
 				do {
@@ -1920,7 +2036,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 						float dirPdf;
 						const bool delta = il.kind == PRGPU_LIGHT_DISTANT;
 						Blob radiance;
-						inf_light_sample(sc, il, d0, d1, wl, L, dirPdf, radiance);
+						inf_light_sample<EXPR>(sc, il, d0, d1, wl, L, dirPdf, radiance);
 						const V3 lpos	 = P + L * sc.scene_radius;
 						const V3 dLP	 = lpos - P;
 						const float sqrD = dot(dLP, dLP);
@@ -2036,7 +2152,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 					}
 					const V3 L			 = normalized(lp - P);
 					const float cosLight = fminf(1.0f, fmaxf(-1.0f, -dot(L, lgp.N)));
-					const Blob radiance	 = spectrum_eval_copy(sc, LE.node, LE.lhs, LE.rhs, wl);
+					const Blob radiance	 = spectrum_eval_copy<EXPR>(sc, LE.node, LE.lhs, LE.rhs, wl);
 					const V3 dLP		 = lp - P;
 					const float sqrD	 = dot(dLP, dLP);
 					const float cosC	 = fabsf(dot(L, N));
@@ -2145,17 +2261,17 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 				} else if ((FEATS & FEAT_DELTA_MATERIALS) && mat.kind == PRGPU_MAT_CONDUCTOR) {
 					// ConductorMaterial::sample (conductor.cpp:54-71): mirror, per-wavelength Fresnel term, no random number
 					pdf_s		   = blob(1);
-					const Blob eta = spectrum_eval<IMG>(sc, mat.ior, wl, gp.uv), kk = spectrum_eval<IMG>(sc, mat.k, wl, gp.uv);
+					const Blob eta = spectrum_eval<IMG, EXPR>(sc, mat.ior, wl, gp.uv), kk = spectrum_eval<IMG, EXPR>(sc, mat.k, wl, gp.uv);
 					Blob fresnel;
 					for (int i = 0; i < 4; ++i)
 						fresnel.v[i] = fresnel_conductor(fabsf(Vt.z), 1.0f, eta.v[i], kk.v[i]);
 					integral_weight = fresnel * albedo_v;
 					Lt				= v3(-Vt.x, -Vt.y, Vt.z);
-					heroCollapsing	= sc.spectra[mat.ior].kind == PRGPU_SPEC_SELLMEIER || sc.spectra[mat.k].kind == PRGPU_SPEC_SELLMEIER;
+					heroCollapsing	= spectrum_varying<EXPR>(sc.spectra[mat.ior]) || spectrum_varying<EXPR>(sc.spectra[mat.k]);
 				} else if (sampleDeltaMat) {
 					// DielectricMaterial::sample (dielectric.cpp:60-114), camera rays
 					pdf_s		  = blob(1);
-					const Blob n2 = spectrum_eval<IMG>(sc, mat.ior, wl, gp.uv);
+					const Blob n2 = spectrum_eval<IMG, EXPR>(sc, mat.ior, wl, gp.uv);
 					float F		  = fresnel_dielectric(Vt.z, DIELECTRIC_AIR, n2.v[0]);
 					if (mat.thin && F < 1.0f)
 						F += (1 - F) * F / (F + 1);
@@ -2164,7 +2280,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 						Lt				= v3(-Vt.x, -Vt.y, Vt.z);
 						integral_weight = rWeight;
 					} else {
-						const Blob tWeight = mat.transmission != INVALID ? spectrum_eval<IMG>(sc, mat.transmission, wl, gp.uv) : rWeight;
+						const Blob tWeight = mat.transmission != INVALID ? spectrum_eval<IMG, EXPR>(sc, mat.transmission, wl, gp.uv) : rWeight;
 						if (mat.thin) {
 							Lt				= -Vt;
 							integral_weight = tWeight;
@@ -2173,7 +2289,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 							integral_weight = (signbit(Lt.z) == signbit(Vt.z)) ? rWeight : tWeight;
 						}
 					}
-					heroCollapsing = sc.spectra[mat.ior].kind == PRGPU_SPEC_SELLMEIER; // isDelta && isSpectralVarying (MaterialData.h:22)
+					heroCollapsing = spectrum_varying<EXPR>(sc.spectra[mat.ior]); // isDelta && isSpectralVarying (MaterialData.h:22)
 				} else if (MIX && mat.kind == PRGPU_MAT_OREN_NAYAR) {
 					// OrenNayarMaterial::sample (orennayar.cpp:69-80): cosine hemisphere around +N, NOT flipped to the viewer's side
 					const float s1 = rng_float(rnd), s2 = rng_float(rnd);

@@ -12,7 +12,8 @@
 #define PR_UV_PARAM
 #define PR_UV_ARG
 #endif
-static __device__ PR_CLOSURE Blob PR_UV(spectrum_eval_cold)(const DevScene& sc, uint32_t id, const Blob& wl PR_UV_PARAM) { return spectrum_eval<PR_CLOSURES_IMG != 0>(sc, id, wl PR_UV_ARG); }
+// (FEAT_EXPR rides with FEAT_IMAGES, render.h: the _uv forms are also the ones that run an expression root's program)
+static __device__ PR_CLOSURE Blob PR_UV(spectrum_eval_cold)(const DevScene& sc, uint32_t id, const Blob& wl PR_UV_PARAM) { return spectrum_eval<PR_CLOSURES_IMG != 0, PR_CLOSURES_IMG != 0>(sc, id, wl PR_UV_ARG); }
 __device__ __forceinline__ Principled PR_UV(principled_closure)(const DevScene& s, const prgpu_material& m, const Blob& wl, const Blob& cie_y PR_UV_PARAM) // createClosure :475-497, ctor :63-84
 {
 	Principled p;
@@ -99,7 +100,7 @@ static __device__ PR_CLOSURE void PR_UV(rough_sample)(const DevScene& s, const p
 	if (mat.kind == PRGPU_MAT_ROUGH_CONDUCTOR) {
 		const float u0 = rng_float(rnd), u1 = rng_float(rnd);
 		Lt				= mf_reflection_sample(d, u0, u1, Vt);
-		hero_collapsing = delta && ((s.spectra[mat.ior].kind == PRGPU_SPEC_SELLMEIER) || (s.spectra[mat.k].kind == PRGPU_SPEC_SELLMEIER));
+		hero_collapsing = delta && (spectrum_varying<PR_CLOSURES_IMG != 0>(s.spectra[mat.ior]) || spectrum_varying<PR_CLOSURES_IMG != 0>(s.spectra[mat.k]));
 		if (!sv_same_hemisphere(Vt, Lt)) { // MaterialSampleOutput::Reject
 			Lt				= v3(0, 0, 0);
 			integral_weight = blob(0);
@@ -116,7 +117,7 @@ static __device__ PR_CLOSURE void PR_UV(rough_sample)(const DevScene& s, const p
 		const Blob spec	 = PR_UV(spectrum_eval_cold)(s, mat.albedo, wl PR_UV_ARG);
 		const Blob trans = mat.transmission != INVALID ? PR_UV(spectrum_eval_cold)(s, mat.transmission, wl PR_UV_ARG) : spec;
 		const Blob ior	 = PR_UV(spectrum_eval_cold)(s, mat.ior, wl PR_UV_ARG);
-		hero_collapsing	 = delta && (s.spectra[mat.ior].kind == PRGPU_SPEC_SELLMEIER);
+		hero_collapsing	 = delta && spectrum_varying<PR_CLOSURES_IMG != 0>(s.spectra[mat.ior]);
 		// RoughDielectricClosure::sample (roughdielectric.cpp:124-137): branch on the hero wavelength's Fresnel term
 		const float F  = fresnel_dielectric(Vt.z, DIELECTRIC_AIR, ior.v[0]);
 		const float ub = rng_float(rnd);

@@ -35,6 +35,7 @@
 #include "datalisp.h"
 #include "image_reader.h"
 #include "setup.h"
+#include "spectral_expr.h"
 
 using prgpu_host::dl::Group;
 using prgpu_host::dl::Value;
@@ -211,10 +212,49 @@ struct Loader {
 	}
 
 	// ---- spectral expressions ----------------------------------------------------------------------------------
-	uint32_t add_spectrum(const prgpu_spectrum& s)
+	std::vector<prgpu_host::ExprInfo> expr_info; // per node of out.spectra (spectral_expr.h): the two bounds of the device evaluator are refused where the node is written
+	uint32_t add_spectrum(const prgpu_spectrum& s, const Group* e = nullptr)
 	{
+		if (e && prgpu_host::spec_is_math(s.kind)) { // no uv-dependent node below a math node (the words smul always had)
+			const std::string name = lower(e->id);
+			for (uint32_t op : { s.lhs, prgpu_host::spec_is_unary(s.kind) ? s.lhs : s.rhs }) {
+				if (out.spectra[op].kind == PRGPU_SPEC_CHECKER)
+					fail(PRGPU_EUNSUPPORTED, where(*e) + ": a checkerboard inside " + name + " is not supported");
+				if (out.spectra[op].kind == PRGPU_SPEC_IMAGE)
+					fail(PRGPU_EUNSUPPORTED, where(*e) + ": an image texture inside " + name + " is not supported");
+			}
+		}
+		expr_info.resize(out.spectra.size()); // (the sky light's albedo nodes are dropped again once they are evaluated)
 		out.spectra.push_back(s);
+		expr_info.push_back(prgpu_host::expr_info_of(s, expr_info, out.spectra.data()));
+		const prgpu_host::ExprInfo& info = expr_info.back();
+		if (e && info.expression && info.need > PRGPU_EXPR_MAX_STACK)
+			fail(PRGPU_EUNSUPPORTED, where(*e) + ": the expression needs an operand stack of " + std::to_string(info.need) + " entries, more than the device evaluator's " + std::to_string(PRGPU_EXPR_MAX_STACK)
+										 + " (PRGPU_EXPR_MAX_STACK)");
+		if (e && info.expression && info.length > PRGPU_EXPR_MAX_PROGRAM)
+			fail(PRGPU_EUNSUPPORTED, where(*e) + ": the expression's program is longer than the device evaluator's " + std::to_string(PRGPU_EXPR_MAX_PROGRAM) + " words (PRGPU_EXPR_MAX_PROGRAM)");
 		return (uint32_t)out.spectra.size() - 1;
+	}
+	// lookupSpectralNode (SceneLoadContext.cpp:201-234) of positional parameter `k` of a math node: default 0, for a missing one too
+	uint32_t math_operand(const Group& e, size_t k, const char* key)
+	{
+		const Value& v = e.at(k);
+		if (v.type == Value::NONE || v.type == Value::BOOL)
+			return spectrum_const(0.0f);
+		const float keep = string_default;
+		string_default	 = 0.0f;
+		const uint32_t id = spectral_node(v, e, key);
+		string_default	 = keep;
+		return id;
+	}
+	// a parameter the reference reads with getNumber(def) unless it isReference() -- an inline group, which would be a scalar node: not built.
+	// (A string is no reference there: getNumber answers the default.)
+	float constant_parameter(const Group& e, size_t k, const char* key, float def)
+	{
+		const Value& v = e.at(k);
+		if (v.type == Value::GROUP)
+			fail(PRGPU_EUNSUPPORTED, where(e) + ": a dynamic :" + key + " (a scalar node) is not supported: " + key + " must be a number");
+		return v.is_number() ? (float)v.number() : def;
 	}
 	static prgpu_spectrum blank(uint32_t kind)
 	{
@@ -256,11 +296,13 @@ struct Loader {
 			return spectrum_const((float)v.number());
 		if (v.type == Value::STRING) {
 			// SceneLoadContext::lookupSpectralNode (SceneLoadContext.cpp:222-232): a string names a (node ...)/(texture ...) block; an
-			// unknown name silently yields the parameter's default.  (node ...) blocks are rejected when they are declared (dispatch), so
-			// every name but a declared texture's is unknown here.
+			// unknown name silently yields the parameter's default.
 			const auto tex = texture_ids.find(v.s);
 			if (tex != texture_ids.end())
 				return tex->second;
+			const auto node = node_ids.find(v.s);
+			if (node != node_ids.end())
+				return node->second;
 			warn(std::string(":") + key + " of " + where(owner) + " names the unknown node '" + v.s + "': default value used (as the reference does)");
 			return spectrum_const(string_default);
 		}
@@ -344,19 +386,52 @@ struct Loader {
 			s.p[2] = n <= 2 ? 0.0f : (n == 3 ? 1.0f : 2.0f);
 			return add_spectrum(s);
 		}
-		if (id == "smul") { // SpectralMathNode.cpp:275: product of two spectral nodes
-			if (e.anonymous_count() != 2)
-				fail(PRGPU_EINVAL, where(e) + ": smul takes two operands");
-			prgpu_spectrum s = blank(PRGPU_SPEC_MUL);
-			s.lhs			 = spectral_node(e.at(0), e, "lhs");
-			s.rhs			 = spectral_node(e.at(1), e, "rhs");
-			if (out.spectra[s.lhs].kind == PRGPU_SPEC_MUL || out.spectra[s.rhs].kind == PRGPU_SPEC_MUL)
-				fail(PRGPU_EUNSUPPORTED, where(e) + ": nested smul is not supported (operands must be leaves)");
-			if (out.spectra[s.lhs].kind == PRGPU_SPEC_CHECKER || out.spectra[s.rhs].kind == PRGPU_SPEC_CHECKER)
-				fail(PRGPU_EUNSUPPORTED, where(e) + ": a checkerboard inside smul is not supported");
-			if (out.spectra[s.lhs].kind == PRGPU_SPEC_IMAGE || out.spectra[s.rhs].kind == PRGPU_SPEC_IMAGE)
-				fail(PRGPU_EUNSUPPORTED, where(e) + ": an image texture inside smul is not supported");
-			return add_spectrum(s);
+		// SpectralMathPlugin::create (SpectralMathNode.cpp:267-331): positional parameters, every operand through lookupSpectralNode with
+		// the default 0.  A product of two leaves is the MUL record it always was; everything else is an expression (include/prgpu.h).
+		static const struct {
+			const char* name;
+			uint32_t kind;
+		} math[] = { { "smul", PRGPU_SPEC_MUL }, { "sadd", PRGPU_SPEC_ADD }, { "ssub", PRGPU_SPEC_SUB }, { "sdiv", PRGPU_SPEC_DIV }, { "sneg", PRGPU_SPEC_NEG },
+					 { "sabs", PRGPU_SPEC_ABS }, { "smax", PRGPU_SPEC_MAX }, { "smin", PRGPU_SPEC_MIN }, { "sburn", PRGPU_SPEC_BURN }, { "sscreen", PRGPU_SPEC_SCREEN },
+					 { "sdodge", PRGPU_SPEC_DODGE }, { "soverlay", PRGPU_SPEC_OVERLAY }, { "ssoftlight", PRGPU_SPEC_SOFTLIGHT }, { "shardlight", PRGPU_SPEC_HARDLIGHT },
+					 { "sblend", PRGPU_SPEC_BLEND }, { "sbrightnesscontrast", PRGPU_SPEC_BRIGHTNESS_CONTRAST } };
+		for (const auto& op : math) {
+			if (id != op.name)
+				continue;
+			prgpu_spectrum s = blank(op.kind);
+			if (op.kind == PRGPU_SPEC_BLEND) { // (sblend factor op1 op2), :309-318
+				s.p[0] = constant_parameter(e, 0, "factor", 0.5f);
+				s.lhs  = math_operand(e, 1, "op1");
+				s.rhs  = math_operand(e, 2, "op2");
+			} else if (op.kind == PRGPU_SPEC_BRIGHTNESS_CONTRAST) { // (sbrightnesscontrast color brightness contrast), :319-326
+				s.lhs  = math_operand(e, 0, "color");
+				s.rhs  = PRGPU_INVALID_ID;
+				s.p[0] = constant_parameter(e, 1, "brightness", 0.0f);
+				s.p[1] = constant_parameter(e, 2, "contrast", 0.0f);
+			} else if (prgpu_host::spec_is_unary(op.kind)) {
+				s.lhs = math_operand(e, 0, "op");
+				s.rhs = PRGPU_INVALID_ID;
+			} else {
+				s.lhs = math_operand(e, 0, op.kind == PRGPU_SPEC_MUL ? "lhs" : "op1");
+				s.rhs = math_operand(e, 1, op.kind == PRGPU_SPEC_MUL ? "rhs" : "op2");
+			}
+			return add_spectrum(s, &e);
+		}
+		if (id == "blackbody") { // BlackbodyPlugin::create (BlackbodyNode.cpp:95-111): a constant temperature is ALWAYS peak-normalised (:106-109)
+			prgpu_spectrum s = blank(PRGPU_SPEC_BLACKBODY);
+			s.p[0]			 = constant_parameter(e, 0, "temperature", 6500.0f);
+			if (!(s.p[0] > 0.0f) || !std::isfinite(s.p[0]))
+				fail(PRGPU_EINVAL, where(e) + ": the temperature must be positive and finite");
+			s.p[1] = prgpu_host::blackbody_norm(s.p[0]);
+			return add_spectrum(s, &e);
+		}
+		if (id == "triangle_peak" || id == "peak") { // TrianglePeakNodePlugin::create (TrianglePeakNode.cpp:81-91)
+			prgpu_spectrum s = blank(PRGPU_SPEC_PEAK);
+			s.p[0]			 = constant_parameter(e, 0, "wavelength", 520.0f);
+			s.p[1]			 = constant_parameter(e, 1, "radius", 2.0f);
+			if (!(s.p[1] > 0.0f) || !std::isfinite(s.p[1]) || !std::isfinite(s.p[0]))
+				fail(PRGPU_EINVAL, where(e) + ": the radius must be positive, radius and wavelength finite");
+			return add_spectrum(s, &e);
 		}
 		if (id == "lookup_index") { // ReflectiveNode.cpp:224-246,387-396: tabulated Sellmeier coefficients (refractiveindex.info)
 			std::string name = lower(e.at(0).type == Value::STRING ? e.at(0).s : get_string(e, "name", "bk7"));
@@ -610,6 +685,38 @@ struct Loader {
 				fail(PRGPU_EINVAL, where(g) + ": texture '" + name + "': colour components must be finite and non-negative");
 		texture_ids[name] = spectrum_image(img.rgb.data(), img.width, img.height, interpolation, wrap[0], wrap[1]);
 	}
+	// ---- (node :name N :type T p0 p1 ...) blocks: SceneLoader::addNode (SceneLoader.cpp:672-716) ------------------------------------
+	std::map<std::string, uint32_t> node_ids; // name -> the spectral node the block declared
+	void add_node(const Group& g)
+	{
+		const Value *nv = g.get("name"), *tv = g.get("type");
+		if (!nv || nv->type != Value::STRING)
+			fail(PRGPU_EINVAL, where(g) + ": node without a name");
+		const std::string name = nv->s;
+		if (node_ids.count(name) || texture_ids.count(name)) // (hasNode: textures are nodes too)
+			fail(PRGPU_EINVAL, where(g) + ": node '" + name + "' already exists");
+		if (!tv || tv->type != Value::STRING)
+			fail(PRGPU_EINVAL, where(g) + ": no type given for node '" + name + "'");
+		const std::string type = lower(tv->s);
+		static const char* const known[] = { "refl", "reflection", "illum", "illumination", "illuminant", "spectrum", "spd", "checkerboard", "grid", "lookup_index", "sellmeier_index",
+											 "smul", "sadd", "ssub", "sdiv", "sneg", "sabs", "smax", "smin", "sburn", "sscreen", "sdodge", "soverlay", "ssoftlight", "shardlight",
+											 "sblend", "sbrightnesscontrast", "blackbody", "triangle_peak", "peak" };
+		if (std::find_if(std::begin(known), std::end(known), [&](const char* k) { return type == k; }) == std::end(known))
+			fail(PRGPU_EUNSUPPORTED, where(g) + ": block is not supported by this backend yet");
+		// the block's parameters are the inline form's (populateObjectParameters: positional and named alike): the same group under the type's id
+		Value v;
+		v.type	   = Value::GROUP;
+		v.g		   = std::make_shared<Group>();
+		v.g->id	   = type;
+		v.g->line  = g.line;
+		for (const auto& entry : g.entries)
+			if (entry.key != "name" && entry.key != "type")
+				v.g->entries.push_back(entry);
+		const float keep = string_default; // (a math node's operands set their own default, 0; a checkerboard's theirs)
+		string_default	 = 0.0f;
+		node_ids[name]	 = spectral_node(v, g, "node");
+		string_default	 = keep;
+	}
 	// an image texture, or a checkerboard that holds one
 	bool holds_image(uint32_t id, int depth = 0) const
 	{
@@ -662,6 +769,8 @@ struct Loader {
 		if (id >= out.spectra.size())
 			return 0.0f;
 		const prgpu_spectrum& n = out.spectra[id];
+		if (id < expr_info.size() && expr_info[id].expression) // an expression: the operators and leaves of spectral_expr.h
+			return prgpu_host::expr_eval_at(out.spectra.data(), (uint32_t)out.spectra.size(), id, wl, [&](const prgpu_spectrum& l, float) { return leaf(l); });
 		if (n.kind == PRGPU_SPEC_MUL && n.lhs < out.spectra.size() && n.rhs < out.spectra.size())
 			return leaf(out.spectra[n.lhs]) * leaf(out.spectra[n.rhs]);
 		return leaf(n);
@@ -2093,7 +2202,7 @@ struct Loader {
 		else if (id == "texture")
 			add_texture(b);
 		else if (id == "node")
-			fail(PRGPU_EUNSUPPORTED, where(b) + ": block is not supported by this backend yet");
+			add_node(b);
 		else if (id == "scene")
 			fail(PRGPU_EINVAL, where(b) + ": invalid inner scene entry");
 		else

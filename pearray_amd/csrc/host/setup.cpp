@@ -12,6 +12,7 @@
 //   filter taps                       filter/FilterCache.h:8-25 + plugins/main/filter/*.cpp
 //   Russian-roulette table            vcm/vcm/RussianRoulette.h:22-35
 #include "setup.h"
+#include "spectral_expr.h"
 
 #include <algorithm>
 #include <array>
@@ -141,6 +142,13 @@ V4 eval_leaf(const prgpu_scene_desc* d, const prgpu_spectrum& n, const V4& wl)
 V4 eval_spectrum(const prgpu_scene_desc* d, uint32_t id, const V4& wl)
 {
 	const prgpu_spectrum& n = d->spectra[id];
+	if (n.kind > PRGPU_SPEC_IMAGE || (n.kind == PRGPU_SPEC_MUL && (spec_is_math(d->spectra[n.lhs].kind) || spec_is_math(d->spectra[n.rhs].kind) || d->spectra[n.lhs].kind > PRGPU_SPEC_IMAGE || d->spectra[n.rhs].kind > PRGPU_SPEC_IMAGE))) {
+		// an expression: the operators and the two leaves of spectral_expr.h, the statements of expr_eval on the device
+		V4 r;
+		for (int k = 0; k < 4; ++k)
+			r.v[k] = expr_eval_at(d->spectra, d->n_spectra, id, wl.v[k], [&](const prgpu_spectrum& leaf, float w) { return eval_leaf(d, leaf, V4{ { w, w, w, w } }).v[0]; });
+		return r;
+	}
 	if (n.kind != PRGPU_SPEC_MUL)
 		return eval_leaf(d, n, wl);
 	const V4 a = eval_leaf(d, d->spectra[n.lhs], wl), b = eval_leaf(d, d->spectra[n.rhs], wl);
@@ -165,7 +173,10 @@ void spectral_range(const prgpu_scene_desc* d, uint32_t id, float& start, float&
 	if (n.kind == PRGPU_SPEC_TABLE) {
 		start = n.wl_start;
 		end	  = n.wl_end;
-	} else if (n.kind == PRGPU_SPEC_MUL) {
+	} else if (spec_is_math(n.kind) && spec_is_unary(n.kind)) { // sneg, sabs pass their operand's range through (SpectralMathNode.cpp:24);
+		if (n.kind != PRGPU_SPEC_BRIGHTNESS_CONTRAST)			// brightness / contrast, blackbody and peak do not override spectralRange(): unbounded
+			spectral_range(d, n.lhs, start, end);
+	} else if (spec_is_math(n.kind)) { // the binary nodes and sblend: the union (:54,136)
 		float s0, e0, s1, e1;
 		spectral_range(d, n.lhs, s0, e0);
 		spectral_range(d, n.rhs, s1, e1);
@@ -1084,10 +1095,35 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 		if (E.kind == PRGPU_ENTITY_PLANE && E.n_tris != 2)
 			return bad("a plane entity is exactly two triangles (v0,v1,v3), (v2,v3,v1)");
 	}
+	std::vector<ExprInfo> expr_info; // per node, from its operands' (spectral_expr.h)
+	expr_info.reserve(d->n_spectra);
 	for (uint32_t i = 0; i < d->n_spectra; ++i) {
 		const prgpu_spectrum& n = d->spectra[i];
-		if (n.kind > PRGPU_SPEC_IMAGE)
+		if (n.kind > PRGPU_SPEC_PEAK)
 			return bad("unknown spectrum kind");
+		if (n.kind > PRGPU_SPEC_IMAGE) { // the expression nodes (MUL is checked below, as before)
+			const std::string what = "spectral expression node " + std::to_string(i);
+			if (d->n_spectra > 0x00FFFFFFu)
+				return bad("a scene with spectral expressions holds at most 2^24 - 1 spectral nodes", PRGPU_EUNSUPPORTED);
+			for (int k = 0; k < 4; ++k)
+				if (!std::isfinite(n.p[k]))
+					return bad((what + ": parameters must be finite").c_str());
+			if (n.kind == PRGPU_SPEC_BLACKBODY && !(n.p[0] > 0.0f))
+				return bad((what + ": blackbody temperature must be positive").c_str());
+			if (n.kind == PRGPU_SPEC_PEAK && !(n.p[1] > 0.0f))
+				return bad((what + ": peak radius must be positive").c_str());
+			if (spec_is_math(n.kind)) {
+				const bool unary = spec_is_unary(n.kind);
+				if (n.lhs >= i || (!unary && n.rhs >= i))
+					return bad((what + ": operands must precede the node").c_str());
+				for (uint32_t op : { n.lhs, unary ? n.lhs : n.rhs }) {
+					if (d->spectra[op].kind == PRGPU_SPEC_CHECKER)
+						return bad((what + ": a checkerboard inside a math node is not supported").c_str(), PRGPU_EUNSUPPORTED);
+					if (d->spectra[op].kind == PRGPU_SPEC_IMAGE)
+						return bad((what + ": an image texture inside a math node is not supported").c_str(), PRGPU_EUNSUPPORTED);
+				}
+			}
+		}
 		if (n.kind == PRGPU_SPEC_IMAGE) {
 			if (n.lhs == 0 || n.rhs == 0 || n.lhs > 4096 || n.rhs > 4096)
 				return bad("image texture: width and height must be 1..4096");
@@ -1112,13 +1148,21 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 		if (n.kind == PRGPU_SPEC_MUL) {
 			if (n.lhs >= i || n.rhs >= i)
 				return bad("MUL operands must precede the node");
-			if (d->spectra[n.lhs].kind == PRGPU_SPEC_MUL || d->spectra[n.rhs].kind == PRGPU_SPEC_MUL)
-				return bad("nested MUL spectral nodes are not supported", PRGPU_EUNSUPPORTED);
+			if (d->n_spectra > 0x00FFFFFFu && (spec_is_math(d->spectra[n.lhs].kind) || spec_is_math(d->spectra[n.rhs].kind) || d->spectra[n.lhs].kind == PRGPU_SPEC_SELLMEIER || d->spectra[n.rhs].kind == PRGPU_SPEC_SELLMEIER))
+				return bad("a scene with spectral expressions holds at most 2^24 - 1 spectral nodes", PRGPU_EUNSUPPORTED);
 			if (d->spectra[n.lhs].kind == PRGPU_SPEC_CHECKER || d->spectra[n.rhs].kind == PRGPU_SPEC_CHECKER)
 				return bad("a checkerboard inside a MUL node is not supported", PRGPU_EUNSUPPORTED);
 			if (d->spectra[n.lhs].kind == PRGPU_SPEC_IMAGE || d->spectra[n.rhs].kind == PRGPU_SPEC_IMAGE)
 				return bad("an image texture inside a MUL node is not supported", PRGPU_EUNSUPPORTED);
 		}
+		expr_info.push_back(expr_info_of(n, expr_info, d->spectra));
+		if (expr_info[i].expression && expr_info[i].need > PRGPU_EXPR_MAX_STACK)
+			return bad(("spectral expression node " + std::to_string(i) + ": needs an operand stack of " + std::to_string(expr_info[i].need) + " entries, more than PRGPU_EXPR_MAX_STACK ("
+						+ std::to_string(PRGPU_EXPR_MAX_STACK) + ")")
+						   .c_str(),
+					   PRGPU_EUNSUPPORTED);
+		if (expr_info[i].expression && expr_info[i].length > PRGPU_EXPR_MAX_PROGRAM)
+			return bad(("spectral expression node " + std::to_string(i) + ": its program is longer than PRGPU_EXPR_MAX_PROGRAM (" + std::to_string(PRGPU_EXPR_MAX_PROGRAM) + " words)").c_str(), PRGPU_EUNSUPPORTED);
 	}
 	for (uint32_t i = 0; i < d->n_materials; ++i) {
 		const prgpu_material& m = d->materials[i];
@@ -1256,12 +1300,67 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 			return bad("emission radiance index out of range");
 		{
 			const prgpu_spectrum& r = d->spectra[d->emissions[i].radiance];
-			if (r.kind == PRGPU_SPEC_SELLMEIER
-				|| (r.kind == PRGPU_SPEC_MUL && (d->spectra[r.lhs].kind == PRGPU_SPEC_SELLMEIER || d->spectra[r.rhs].kind == PRGPU_SPEC_SELLMEIER)))
+			if (r.kind == PRGPU_SPEC_SELLMEIER || expr_info[d->emissions[i].radiance].sellmeier) // (alone, or anywhere inside a product or an expression)
 				return bad("a refractive-index node cannot be used as radiance", PRGPU_EUNSUPPORTED);
 		}
 	}
 	return PRGPU_OK;
+}
+
+bool compile_expressions(const prgpu_scene_desc* d, std::vector<prgpu_spectrum>& spectra, std::vector<uint32_t>& programs)
+{
+	spectra.assign(d->spectra, d->spectra + d->n_spectra);
+	programs.clear();
+	std::vector<ExprInfo> info;
+	info.reserve(d->n_spectra);
+	for (uint32_t i = 0; i < d->n_spectra; ++i)
+		info.push_back(expr_info_of(d->spectra[i], info, d->spectra));
+	std::vector<uint8_t> root(d->n_spectra, 0);
+	auto name = [&](uint32_t id) {
+		if (id != PRGPU_INVALID_ID && id < d->n_spectra && info[id].expression)
+			root[id] = 1;
+	};
+	for (uint32_t i = 0; i < d->n_materials; ++i) {
+		const prgpu_material& m = d->materials[i];
+		if (m.kind == PRGPU_MAT_BLEND || m.kind == PRGPU_MAT_ADD) // (their fields name materials, not nodes)
+			continue;
+		name(m.albedo);
+		name(m.ior);
+		name(m.k);
+		name(m.transmission);
+	}
+	for (uint32_t i = 0; i < d->n_emissions; ++i)
+		name(d->emissions[i].radiance);
+	for (uint32_t i = 0; i < d->n_lights; ++i)
+		if (d->lights[i].kind != PRGPU_LIGHT_SKY) {
+			name(d->lights[i].radiance);
+			name(d->lights[i].background);
+		}
+	for (uint32_t i = 0; i < d->n_spectra; ++i)
+		if (d->spectra[i].kind == PRGPU_SPEC_CHECKER) {
+			name(d->spectra[i].lhs);
+			name(d->spectra[i].rhs);
+		}
+	bool any = false;
+	for (uint32_t i = 0; i < d->n_spectra; ++i) {
+		if (!root[i])
+			continue;
+		any = true;
+		const size_t first = programs.size();
+		expr_emit(d->spectra, info, i, programs);
+		spectra[i].table_offset = uint32_t(d->n_spectral_table_values + first);
+		spectra[i].table_count	= uint32_t(programs.size() - first);
+		spectra[i].wl_start		= info[i].varying ? 1.0f : 0.0f;
+		spectra[i].wl_end		= 0.0f;
+	}
+	// A node that is no root runs no program, whatever the caller left in fields its kind does not use -- in EVERY scene: the top row's
+	// kernels look at table_count of a MUL whether or not the scene has a root (a scene gets there for a disk or a light path expression too).
+	for (uint32_t i = 0; i < d->n_spectra; ++i)
+		if (!root[i] && (spectra[i].kind == PRGPU_SPEC_MUL || spectra[i].kind > PRGPU_SPEC_IMAGE)) {
+			spectra[i].table_offset = spectra[i].table_count = 0;
+			spectra[i].wl_start = spectra[i].wl_end = 0.0f;
+		}
+	return any;
 }
 
 int build_tables(const prgpu_scene_desc* d, HostTables& t, std::string& err)

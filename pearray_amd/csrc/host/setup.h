@@ -45,6 +45,13 @@ struct HostTables {
 // returns PRGPU_OK or an error code with `err` set
 int validate_desc(const prgpu_scene_desc* d, std::string& err);
 int build_tables(const prgpu_scene_desc* d, HostTables& t, std::string& err);
+// Spectral expressions (include/prgpu.h; spectral_expr.h): the device's copy of the node array and the postfix programs of the expression
+// roots -- the nodes a material, an emission, an infinite light or a CHECKER operand names that are neither a plain leaf nor a MUL of two.
+// A root's copy carries its program: table_count words at word table_offset of the device's table array, where `programs` is appended
+// behind the scene's `n_table_values` floats; wl_start = 1 when the expression is spectral varying.  Every other MUL / expression record's
+// copy has those fields (which its kind does not use, and a caller may have left anything in) zeroed: the device takes a non-zero
+// table_count there for a program.  Returns whether the scene has a root; `spectra` is what the device gets either way.
+bool compile_expressions(const prgpu_scene_desc* d, std::vector<prgpu_spectrum>& spectra, std::vector<uint32_t>& programs);
 // Morton-ordered list of the owned pixels (StreamPipeline.cpp:83-133 walks each tile in Morton order)
 void owned_pixels_morton(uint32_t W, uint32_t H, const prgpu_tile* tiles, uint32_t n_tiles, std::vector<uint32_t>& pixels);
 

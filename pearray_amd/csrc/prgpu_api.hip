@@ -461,18 +461,34 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 		UP(up, rec);
 		sc.shade_rec = reinterpret_cast<const float4*>(up);
 	}
+	// spectral expressions: the roots' programs go behind the tables, the node array's copy names them (setup.h, compile_expressions);
+	// the copy is what the device gets in every scene: it has the fields a MUL does not use zeroed, which the top row's kernels look at
+	std::vector<prgpu_spectrum> dev_spectra;
+	std::vector<uint32_t> programs;
+	const bool has_expr				 = prgpu_host::compile_expressions(d, dev_spectra, programs);
+	const prgpu_spectrum* spectra_up = dev_spectra.data();
+	if (has_expr && uint64_t(d->n_spectral_table_values) + programs.size() > 0xFFFFFFFFull)
+		return fail(PRGPU_EUNSUPPORTED, "the scene's spectral tables and expression programs exceed the table array");
 	{
 		std::vector<prd::DevMaterial> mats(std::max<uint32_t>(1, d->n_materials));
 		std::memset(mats.data(), 0, mats.size() * sizeof(prd::DevMaterial));
 		for (uint32_t i = 0; i < d->n_materials; ++i) {
 			mats[i].m	   = d->materials[i];
-			mats[i].albedo = d->spectra[d->materials[i].albedo];
+			mats[i].albedo = spectra_up[d->materials[i].albedo];
 		}
 		UP(sc.materials, mats);
 	}
 	UP(sc.emissions, d->emissions, d->n_emissions);
-	UP(sc.spectra, d->spectra, d->n_spectra);
-	UP(sc.tables, d->spectral_tables, d->n_spectral_table_values);
+	UP(sc.spectra, spectra_up, d->n_spectra);
+	if (has_expr) {
+		std::vector<float> tables(size_t(d->n_spectral_table_values) + programs.size());
+		if (d->n_spectral_table_values)
+			std::memcpy(tables.data(), d->spectral_tables, size_t(d->n_spectral_table_values) * sizeof(float));
+		std::memcpy(tables.data() + d->n_spectral_table_values, programs.data(), programs.size() * sizeof(uint32_t));
+		UP(sc.tables, tables);
+	} else {
+		UP(sc.tables, d->spectral_tables, d->n_spectral_table_values);
+	}
 	UP(sc.light_entity, t.light_entity);
 	UP(sc.light_cdf, t.light_cdf);
 	{ // flattened area-light records (DevLight + one record per light triangle)
@@ -492,10 +508,10 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 			L.tri_offset  = (uint32_t)(ltris.size() / prd::LIGHT_TRI_FLOATS);
 			L.has_normals = E.has_normals;
 			L.radiance	  = d->emissions[E.emission].radiance;
-			L.node		  = d->spectra[L.radiance];
+			L.node		  = spectra_up[L.radiance];
 			if (L.node.kind == PRGPU_SPEC_MUL) {
-				L.lhs = d->spectra[L.node.lhs];
-				L.rhs = d->spectra[L.node.rhs];
+				L.lhs = spectra_up[L.node.lhs];
+				L.rhs = spectra_up[L.node.rhs];
 			}
 			L.vol_scale	  = E.vol_scale;
 			if (E.kind == PRGPU_ENTITY_MESH) {
@@ -555,6 +571,8 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 			sc.features |= prd::FEAT_TEXTURES;
 		else if (d->spectra[i].kind == PRGPU_SPEC_IMAGE) // the lookup lives in the top variant only
 			sc.features |= prd::FEAT_TEXTURES | prd::FEAT_IMAGES;
+	if (has_expr) // the evaluator lives in the top variant only
+		sc.features |= prd::FEAT_EXPR;
 	for (uint32_t e = 0; e < d->n_entities; ++e)
 		if (d->entities[e].has_uvs && d->uvs && d->entities[e].kind == PRGPU_ENTITY_MESH)
 			sc.features |= prd::FEAT_TEXTURES; // UV-derived tangent frames need the full variant
@@ -575,7 +593,7 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 		else if (d->entities[e].kind == PRGPU_ENTITY_DISK)
 			sc.features |= prd::FEAT_DISKS;
 	// measurement aid: run a scene with a larger kernel variant than it needs (same results; LPE and quadrics need data the scene does not have)
-	sc.features |= read_knobs().force_features & prd::FEAT_ALL & ~(prd::FEAT_LPE | prd::FEAT_QUADRICS | prd::FEAT_DISKS | prd::FEAT_IMAGES | prd::FEAT_MIX_MATERIALS);
+	sc.features |= read_knobs().force_features & prd::FEAT_ALL & ~(prd::FEAT_LPE | prd::FEAT_QUADRICS | prd::FEAT_DISKS | prd::FEAT_IMAGES | prd::FEAT_MIX_MATERIALS | prd::FEAT_EXPR);
 	sc.scene_radius	 = t.scene_radius;
 	sc.wl_cdf_size	 = (uint32_t)t.wl_cdf.size();
 	sc.wl_u_offset	 = t.wl_u_offset;

@@ -7,6 +7,7 @@ hot path evaluates.  The description is plain data; the same object can be given
 """
 import ctypes as C
 import json
+import math
 import os
 
 import numpy as np
@@ -123,6 +124,45 @@ class SceneBuilder:
 
     def smul(self, a, b):
         return self._add_spec(kind=abi.SPEC_MUL, lhs=a, rhs=b)
+
+    def spectrum_op(self, name, *operands):
+        """A spectral math node by the reference's name (SpectralMathNode.cpp:267-331), with its positional parameters:
+        ("sadd", a, b) and the other binary ones, ("sneg", a), ("sabs", a), ("sblend", factor, a, b),
+        ("sbrightnesscontrast", color, brightness, contrast).  Operands are node ids; factor, brightness and contrast are numbers.
+        The record is the one the .prc loader writes for the inline form."""
+        kind = abi.SPEC_OPS[name.lower()]
+        if kind == abi.SPEC_BLEND:
+            factor, a, b = operands
+            return self._add_spec(kind=kind, lhs=a, rhs=b, p=[float(factor)])
+        if kind == abi.SPEC_BRIGHTNESS_CONTRAST:
+            color, brightness, contrast = operands
+            return self._add_spec(kind=kind, lhs=color, rhs=abi.INVALID_ID, p=[float(brightness), float(contrast)])
+        if kind in (abi.SPEC_NEG, abi.SPEC_ABS):
+            (a,) = operands
+            return self._add_spec(kind=kind, lhs=a, rhs=abi.INVALID_ID)
+        a, b = operands
+        return self._add_spec(kind=kind, lhs=a, rhs=b)
+
+    @staticmethod
+    def _planck(lambda_nm, temperature):
+        """blackbody (core/spectral/Blackbody.h:11-28): float32 wavelength in metres, Planck's law in double with expm1, cast to float32"""
+        c, h, kb = 299792458.0, 6.62607004081e-34, 1.3806485279e-23
+        lam = float(np.float32(lambda_nm) * np.float32(1e-9))
+        temp = float(np.float32(temperature))
+        c1 = 2 * h * c * c
+        c2 = h * c / kb
+        lam5 = lam * (lam * lam) * (lam * lam)
+        return np.float32((c1 / lam5) / math.expm1(c2 / (lam * temp)))
+
+    def spectrum_blackbody(self, temperature=6500.0):
+        """(blackbody T), BlackbodyNode.cpp: always normalised to a peak of 1 (normFactor, :8-14, in float32)"""
+        t = np.float32(temperature)
+        norm = np.float32(1) / self._planck(np.float32(2.897771955e+6) / t, t)
+        return self._add_spec(kind=abi.SPEC_BLACKBODY, p=[float(t), float(norm)])
+
+    def spectrum_peak(self, wavelength=520.0, radius=2.0):
+        """(peak wavelength radius) / (triangle_peak ...), TrianglePeakNode.cpp: max(0, 1 - |lambda - wavelength| / radius)"""
+        return self._add_spec(kind=abi.SPEC_PEAK, p=[float(wavelength), float(radius)])
 
     IMAGE_WRAPS = {"black": 0, "clamp": 1, "periodic": 2, "mirror": 3}
 

@@ -37,6 +37,10 @@ SCENE = """; seed scene of tools/fuzz_loader.py
   (material :name 'glass' :type 'glass' :index (lookup_index "bk7") :specularity 1)
   (material :name 'metal' :type 'roughconductor' :roughness 0.2 :eta 0.2 :k 3.9)
   (material :name 'table' :type 'diffuse' :albedo (spectrum :start 400 :end 700 0.1 0.2 0.4 0.8 0.6 0.3))
+  (node :name 'warm' :type 'smul' (blackbody 3200) 0.5)
+  (node :name 'mixed' :type 'sblend' 0.25 'warm' (sbrightnesscontrast (refl 0.2 0.5 0.7) 0.1 -0.2))
+  (emission :name 'bulb' :type 'standard' :radiance (smul (smul 'warm' 40) (peak 600 150)))
+  (material :name 'tinted' :type 'diffuse' :albedo (checkerboard 'mixed' (smax (sneg (sabs (ssub 0.2 (refl 0.9 0.4 0.1)))) (sdiv (sburn 0.3 0.4) (sadd (triangle_peak) 2))) 4))
   (mesh :name 'quad' (attribute :type 'p' [-1,-1,0],[1,-1,0],[1,1,0],[-1,1,0]) (attribute :type 'n' [0,0,1],[0,0,1],[0,0,1],[0,0,1])
         (attribute :type 't' [0,0],[1,0],[1,1],[0,1]) (faces [0,1,2],[0,2,3]) (materials 0, 0))
   (embed :loader 'obj' :file 'seed.obj' :name 'obj')
@@ -115,7 +119,8 @@ def serialized(version=4, double=False, with_normals=True):
 SEEDS = {"seed.obj": OBJ.encode(), "seed_a.ply": ply("ascii"), "seed_l.ply": ply("binary_little_endian"), "seed_b.ply": ply("binary_big_endian"),
          "seed.serialized": serialized(), "seed_inc.prc": INCLUDE.encode()}
 TOKENS = [b"(", b")", b"[", b"]", b"'", b'"', b":", b",", b";", b"-", b"1e39", b"nan", b"inf", b"-1", b"0", b"4294967296", b"99999999999999999999", b"(embed", b"(include 'scene.prc')",
-          b":shape 9", b":radius -1", b"(refl", b"(smul", b"\x00", b"\xff", b"\n", b"true", b"(spectrum :start 700 :end 400 1 2)", b"(mesh", b"(faces [0,1,99])", b":lpe 'C((('"]
+          b":shape 9", b":radius -1", b"(refl", b"(smul", b"\x00", b"\xff", b"\n", b"true", b"(spectrum :start 700 :end 400 1 2)", b"(mesh", b"(faces [0,1,99])", b":lpe 'C((('",
+          b"(node :name 'warm' :type 'sadd' 'warm' 'mixed')", b"(blackbody", b"(sblend", b"(sadd 'mixed'", b"(peak 500 0)", b":type 'sneg'"]
 
 
 def mutate(data, rng):
