@@ -13,6 +13,7 @@
 
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 namespace prd {
@@ -240,42 +241,62 @@ __device__ __forceinline__ void pad_box(float* lo, float* hi)
 // in the Morton order of the entities' centres.
 __global__ void k_depth_and_flags(int n, const int* __restrict__ parent, const int* __restrict__ range_first, const int* __restrict__ range_last,
 								  uint32_t* __restrict__ inner_flag /* n-1: records of the even-depth collapse */, uint32_t* __restrict__ odd_flag /* ... of the odd-depth one */,
-								  uint32_t* __restrict__ leaf_flag /* n */, uint32_t* __restrict__ leaf_count /* n */, uint32_t* __restrict__ max_record_depth /* [2]: even, odd */)
+								  uint32_t* __restrict__ leaf_flag /* n */, uint32_t* __restrict__ leaf_count /* n */, uint32_t* __restrict__ max_record_depth /* [2]: even, odd */,
+								  int leaf_max /* the leaf policy: 3 or 1 */, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri, const float* __restrict__ boxes,
+								  double* __restrict__ leaf_area /* [2]: summed area of the boxes of the 128-byte leaves, of the single leaves */)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	double a128 = 0.0, a64 = 0.0; // the leaf boxes' areas: the expected leaf visits of a ray through the scene's box, times the root's area (build_lbvh prices them)
 	if (i < n - 1) {
 		int depth = 0;
 		for (int p = parent[i]; p >= 0; p = parent[p])
 			++depth;
 		const int cnt = range_last[i] - range_first[i] + 1;
-		inner_flag[i] = ((depth & 1) == 0 && cnt > 3) ? 1u : 0u;
-		odd_flag[i]	  = (((depth & 1) == 1 || i == 0) && cnt > 3) ? 1u : 0u; // (the root is a record of two children there)
+		inner_flag[i] = ((depth & 1) == 0 && cnt > leaf_max) ? 1u : 0u;
+		odd_flag[i]	  = (((depth & 1) == 1 || i == 0) && cnt > leaf_max) ? 1u : 0u; // (the root is a record of two children there)
 		if (inner_flag[i])
 			atomicMax(max_record_depth, (uint32_t)depth / 2u); // records above this one on its way from the root
 		if (odd_flag[i])
 			atomicMax(max_record_depth + 1, ((uint32_t)depth + 1u) / 2u);
-		if (cnt <= 3) {
+		if (cnt <= leaf_max) {
 			const int p	   = parent[i];
-			const int pcnt = range_last[p] - range_first[p] + 1; // i != root here because cnt(root) = n > 3
-			if (pcnt > 3) {
+			const int pcnt = range_last[p] - range_first[p] + 1; // i != root here because cnt(root) = n > leaf_max
+			if (pcnt > leaf_max) {
 				leaf_flag[range_first[i]]  = 1u;
 				leaf_count[range_first[i]] = (uint32_t)cnt;
+				const double dx = (double)boxes[6 * i + 3] - boxes[6 * i], dy = (double)boxes[6 * i + 4] - boxes[6 * i + 1], dz = (double)boxes[6 * i + 5] - boxes[6 * i + 2];
+				a128 += dx * dy + dy * dz + dz * dx;
 			}
 		}
 	}
 	if (i < n) { // single triangles hanging directly below a big node
 		const int p	   = parent[(n - 1) + i];
 		const int pcnt = range_last[p] - range_first[p] + 1;
-		if (pcnt > 3) {
+		if (pcnt > leaf_max) {
 			leaf_flag[i]  = 1u;
 			leaf_count[i] = 1u;
+			float lo[3], hi[3];
+			tri_box(wv, sorted_tri[i], lo, hi);
+			const double dx = (double)hi[0] - lo[0], dy = (double)hi[1] - lo[1], dz = (double)hi[2] - lo[2];
+			(leaf_max == 1 && wv[3 * sorted_tri[i]].w == 0.0f ? a64 : a128) += dx * dy + dy * dz + dz * dx;
 		}
+	}
+	for (int o = 32; o > 0; o >>= 1) {
+		a128 += __shfl_down(a128, o, 64);
+		a64 += __shfl_down(a64, o, 64);
+	}
+	if ((threadIdx.x & 63) == 0) {
+		if (a128 != 0.0)
+			atomicAdd(leaf_area, a128);
+		if (a64 != 0.0)
+			atomicAdd(leaf_area + 1, a64);
 	}
 }
 
 struct ChildRef {
 	float lo[3], hi[3];
 	bool leaf;
+	bool single; // a leaf of the single kind (one triangle in one unit; leaf policy 1, triangles only)
 	uint32_t id; // leaf: compacted leaf index (leaf_idx of its first sorted triangle); inner: compacted inner index (inner_idx of the radix node)
 	int node;	 // the radix-tree child code the subtree came from (>= 0 internal, < 0 single triangle ~pos)
 	int count;	 // triangles below it
@@ -286,8 +307,22 @@ constexpr int MAX_WIDE = 6; // children an inner record can hold at most
 // eight scenes rendered with both trees (profiles/r05_bvh_width.log) -- six-wide wins where estimate6 / estimate4 <= 0.66 (meshes of uneven
 // density, small scenes: - 3 .. - 7 % time), loses where it is >= 0.76 (uniform triangle soups: + 5 .. + 10 %).
 constexpr double WIDE_STEP_COST = 1.35;
+// What a step on a 128-byte leaf (up to three watertight tests, 128 bytes) and one on a single leaf (one test, 64 bytes) cost against a step on a
+// four-wide inner record: the instrumented path kernel's own time split (share of the wave time spent in leaf steps / leaf records fetched, against
+// the same for inner steps; profiles/r06_single_leaf_ab.log, rays weighted 2 closest : 1 occlusion on C4, 1 : 1 on C5) --
+//   C4, 128-byte leaves: 0.291 x 9.75 ms / 9.94 records against 0.384 x 9.75 / 42.67 = 3.25;  C4, single leaves: 0.124 x 9.11 / 6.20 against 0.507 x 9.11 / 49.48 = 1.95;
+//   C5 (six-wide: x 1.35), 128-byte leaves: 2.81 x 1.35 = 3.8;  C5, single leaves: 1.48 x 1.35 = 2.0.
+// (The three-test leaf step is dearer per record than its instruction count says because it runs at a lane utilisation of 0.52.)
+// The price of a tree = expected inner records per ray x 1 (x WIDE_STEP_COST six-wide) + expected 128-byte-leaf records x LEAF3_STEP_COST + expected
+// single-leaf records x LEAF1_STEP_COST (the expected records are summed surface areas over the root's: k_area_sum, k_depth_and_flags).  Eleven scenes
+// rendered under both policies (the same log; repeated runs of one tree differ by up to 2.3 % in that job): single leaves win by more than that only at
+// price1 / price3 <= 0.81 (C4 0.78 -> - 6.6 % time, a 100 k soup 0.81 -> - 7.7 %); a 4 M soup at 0.80 is even (+ 1.0 %) and 1 M triangles in clusters at
+// 0.84 gain 2.7 %, both inside the spread; they lose where the ratio is >= 1.06 (meshes and the Cornell boxes: C5 1.08 -> + 5.9 %, terrain 1.06 -> + 2.8 %,
+// spheres 1.10 -> + 7.4 %, box 1.17 -> + 7.8 %, stacked sheets 1.22 -> + 61 %).  Nothing was measured between 0.84 and 1.06.  LEAF_MARGIN = 0.82 takes
+// single leaves where the evidence is a win or, at worst, even (the three uniform soups) and keeps today's leaves for everything above, clusters included.
+constexpr double LEAF3_STEP_COST = 3.5, LEAF1_STEP_COST = 2.0, LEAF_MARGIN = 0.82;
 // the subtree `c` (radix-tree child code: >= 0 internal, < 0 single triangle ~pos) as a child of an inner record
-__device__ __forceinline__ ChildRef make_child(int c, bool& expandable, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri,
+__device__ __forceinline__ ChildRef make_child(int c, bool& expandable, int leaf_max, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri,
 											   const int* __restrict__ range_first, const int* __restrict__ range_last, const float* __restrict__ boxes,
 											   const uint32_t* __restrict__ inner_idx, const uint32_t* __restrict__ leaf_idx)
 {
@@ -295,10 +330,12 @@ __device__ __forceinline__ ChildRef make_child(int c, bool& expandable, const fl
 	r.node	   = c;
 	expandable = false;
 	r.count	   = 1;
+	r.single   = false;
 	if (c < 0) {
 		tri_box(wv, sorted_tri[~c], r.lo, r.hi);
-		r.leaf = true;
-		r.id   = leaf_idx[~c];
+		r.leaf	 = true;
+		r.single = leaf_max == 1 && wv[3 * sorted_tri[~c]].w == 0.0f; // (an analytic sphere or disk keeps the 128-byte leaf)
+		r.id	 = leaf_idx[~c];
 	} else {
 		for (int a = 0; a < 3; ++a) {
 			r.lo[a] = boxes[6 * c + a];
@@ -306,7 +343,7 @@ __device__ __forceinline__ ChildRef make_child(int c, bool& expandable, const fl
 		}
 		const int cnt = range_last[c] - range_first[c] + 1;
 		r.count		  = cnt;
-		if (cnt <= 3) {
+		if (cnt <= leaf_max) {
 			r.leaf = true;
 			r.id   = leaf_idx[range_first[c]];
 		} else {
@@ -318,8 +355,8 @@ __device__ __forceinline__ ChildRef make_child(int c, bool& expandable, const fl
 	pad_box(r.lo, r.hi);
 	return r;
 }
-// The children of inner record i, LEAVES FIRST (a record's children lie contiguously from one base unit and leaves are 128-byte
-// aligned: base even, leaves of two units each first, inner records of one unit after them), otherwise in radix-tree order.
+// The children of inner record i, LEAVES FIRST (a record's children lie contiguously from one base unit and 128-byte leaves are 128-byte
+// aligned: base even, those leaves of two units each first, then the single leaves and the inner records of one unit each), otherwise in radix-tree order.
 // width == 0 | -1: the PARITY collapse -- the radix node's grandchildren; inner records are the radix nodes at even depth (0) or at odd depth
 // and the root (-1: k_depth_and_flags marks both sets, build_lbvh takes the one whose records a ray visits less).
 // width >= 2: the GREEDY collapse -- start from the two radix children and, while fewer than `width`, replace the child of largest
@@ -329,7 +366,7 @@ __device__ __forceinline__ float half_area(const ChildRef& c)
 	const float dx = c.hi[0] - c.lo[0], dy = c.hi[1] - c.lo[1], dz = c.hi[2] - c.lo[2];
 	return dx * dy + dy * dz + dz * dx;
 }
-__device__ int gather_children(int i, ChildRef* ch, int width, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri, const int* __restrict__ left,
+__device__ int gather_children(int i, ChildRef* ch, int width, int leaf_max, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri, const int* __restrict__ left,
 							   const int* __restrict__ right, const int* __restrict__ range_first, const int* __restrict__ range_last,
 							   const float* __restrict__ boxes, const uint32_t* __restrict__ inner_idx, const uint32_t* __restrict__ leaf_idx)
 {
@@ -339,19 +376,19 @@ __device__ int gather_children(int i, ChildRef* ch, int width, const float4* __r
 		for (int side = 0; side < 2; ++side) {
 			const int c = side == 0 ? left[i] : right[i];
 			bool expandable;
-			const ChildRef direct = make_child(c, expandable, wv, sorted_tri, range_first, range_last, boxes, inner_idx, leaf_idx);
+			const ChildRef direct = make_child(c, expandable, leaf_max, wv, sorted_tri, range_first, range_last, boxes, inner_idx, leaf_idx);
 			if (!expandable || (width < 0 && i == 0)) { // (odd-depth collapse: the root's two children are records themselves)
 				tmp[nc++] = direct;
 			} else { // odd-depth internal node with > 3 triangles: pull its two children up
 				bool e2;
-				tmp[nc++] = make_child(left[c], e2, wv, sorted_tri, range_first, range_last, boxes, inner_idx, leaf_idx);
-				tmp[nc++] = make_child(right[c], e2, wv, sorted_tri, range_first, range_last, boxes, inner_idx, leaf_idx);
+				tmp[nc++] = make_child(left[c], e2, leaf_max, wv, sorted_tri, range_first, range_last, boxes, inner_idx, leaf_idx);
+				tmp[nc++] = make_child(right[c], e2, leaf_max, wv, sorted_tri, range_first, range_last, boxes, inner_idx, leaf_idx);
 			}
 		}
 	} else {
 		bool ex[MAX_WIDE];
-		tmp[0] = make_child(left[i], ex[0], wv, sorted_tri, range_first, range_last, boxes, inner_idx, leaf_idx);
-		tmp[1] = make_child(right[i], ex[1], wv, sorted_tri, range_first, range_last, boxes, inner_idx, leaf_idx);
+		tmp[0] = make_child(left[i], ex[0], leaf_max, wv, sorted_tri, range_first, range_last, boxes, inner_idx, leaf_idx);
+		tmp[1] = make_child(right[i], ex[1], leaf_max, wv, sorted_tri, range_first, range_last, boxes, inner_idx, leaf_idx);
 		nc	   = 2;
 		while (nc < width) {
 			// the largest child; of equally large ones (coincident geometry: identical boxes all the way down) the one with the most triangles,
@@ -372,14 +409,17 @@ __device__ int gather_children(int i, ChildRef* ch, int width, const float4* __r
 				tmp[k] = tmp[k - 1];
 				ex[k]  = ex[k - 1];
 			}
-			tmp[best]	  = make_child(left[c], ex[best], wv, sorted_tri, range_first, range_last, boxes, inner_idx, leaf_idx);
-			tmp[best + 1] = make_child(right[c], ex[best + 1], wv, sorted_tri, range_first, range_last, boxes, inner_idx, leaf_idx);
+			tmp[best]	  = make_child(left[c], ex[best], leaf_max, wv, sorted_tri, range_first, range_last, boxes, inner_idx, leaf_idx);
+			tmp[best + 1] = make_child(right[c], ex[best + 1], leaf_max, wv, sorted_tri, range_first, range_last, boxes, inner_idx, leaf_idx);
 			++nc;
 		}
 	}
 	int n = 0;
 	for (int k = 0; k < nc; ++k)
-		if (tmp[k].leaf)
+		if (tmp[k].leaf && !tmp[k].single)
+			ch[n++] = tmp[k];
+	for (int k = 0; k < nc; ++k)
+		if (tmp[k].single)
 			ch[n++] = tmp[k];
 	for (int k = 0; k < nc; ++k)
 		if (!tmp[k].leaf)
@@ -402,7 +442,7 @@ __global__ void k_area_sum(int n, const uint32_t* __restrict__ flag, const float
 		atomicAdd(sum, a);
 }
 // Greedy collapse, one level of the top-down pass: the inner children of the records in `front` are records themselves
-__global__ void k_mark_records(int n_front, const int* __restrict__ front, int width, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri,
+__global__ void k_mark_records(int n_front, const int* __restrict__ front, int width, int leaf_max, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri,
 							   const int* __restrict__ left, const int* __restrict__ right, const int* __restrict__ range_first, const int* __restrict__ range_last,
 							   const float* __restrict__ boxes, uint32_t* __restrict__ inner_flag, int* __restrict__ next, uint32_t* __restrict__ n_next,
 							   uint32_t* __restrict__ stack_bound /* per radix node: entries a walk can hold when it reaches the record */, uint32_t* __restrict__ max_stack_bound)
@@ -411,7 +451,7 @@ __global__ void k_mark_records(int n_front, const int* __restrict__ front, int w
 	if (t >= n_front)
 		return;
 	ChildRef ch[MAX_WIDE];
-	const int nc = gather_children(front[t], ch, width, wv, sorted_tri, left, right, range_first, range_last, boxes, inner_flag /* ids unused here */, inner_flag);
+	const int nc = gather_children(front[t], ch, width, leaf_max, wv, sorted_tri, left, right, range_first, range_last, boxes, inner_flag /* ids unused here */, inner_flag);
 	// a step on this record pushes at most nc - 1 entries on top of what the walk already holds
 	const uint32_t below = stack_bound[front[t]] + (uint32_t)(nc - 1);
 	atomicMax(max_stack_bound, below);
@@ -496,7 +536,7 @@ __device__ void write_inner_q(Rec64* __restrict__ rec, const ChildRef* ch, int n
 			w[7 + a] |= h << (8 * k); // q1.w, q2.xy = hi.x, hi.y, hi.z
 		}
 		const int src = used ? k : 0; // unused slot: child 0's payload (a valid record whatever happens)
-		w[11] |= ((offs[src] << REC_UNIT_SHIFT) | (ch[src].leaf ? REC_LEAF_BIT : 0u)) << (8 * k);
+		w[11] |= ((offs[src] << REC_UNIT_SHIFT) | (ch[src].leaf ? REC_LEAF_BIT : 0u) | (ch[src].single ? REC_SINGLE_BIT : 0u)) << (8 * k);
 	}
 	w[10]	   = base_unit << REC_UNIT_SHIFT;
 	for (int k = 4; k < 6; ++k) { // q3: children 4, 5 (inverted boxes in a 4-wide tree, whose steps do not load it)
@@ -508,7 +548,7 @@ __device__ void write_inner_q(Rec64* __restrict__ rec, const ChildRef* ch, int n
 		w[13] |= (hx << (8 * j)) | (hy << (16 + 8 * j));
 		w[14] |= (lz << (8 * j)) | (hz << (16 + 8 * j));
 		const int src = used ? k : 0;
-		w[15] |= ((offs[src] << REC_UNIT_SHIFT) | (ch[src].leaf ? REC_LEAF_BIT : 0u)) << (8 * j);
+		w[15] |= ((offs[src] << REC_UNIT_SHIFT) | (ch[src].leaf ? REC_LEAF_BIT : 0u) | (ch[src].single ? REC_SINGLE_BIT : 0u)) << (8 * j);
 	}
 	uint4* dst = reinterpret_cast<uint4*>(rec);
 	for (int q = 0; q < 4; ++q)
@@ -516,7 +556,8 @@ __device__ void write_inner_q(Rec64* __restrict__ rec, const ChildRef* ch, int n
 }
 
 // 6a. units the children of inner record i occupy (even: the next record's leaves stay 128-byte aligned)
-__global__ void k_group_sizes(int n, int width, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri, const int* __restrict__ left,
+__device__ __forceinline__ uint32_t child_units(const ChildRef& c) { return c.leaf && !c.single ? 2u : 1u; }
+__global__ void k_group_sizes(int n, int width, int leaf_max, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri, const int* __restrict__ left,
 							  const int* __restrict__ right, const int* __restrict__ range_first, const int* __restrict__ range_last,
 							  const float* __restrict__ boxes, const uint32_t* __restrict__ inner_flag, const uint32_t* __restrict__ inner_idx,
 							  const uint32_t* __restrict__ leaf_idx, uint32_t* __restrict__ gsize)
@@ -525,14 +566,14 @@ __global__ void k_group_sizes(int n, int width, const float4* __restrict__ wv, c
 	if (i >= n - 1 || !inner_flag[i])
 		return;
 	ChildRef ch[MAX_WIDE];
-	const int nc = gather_children(i, ch, width, wv, sorted_tri, left, right, range_first, range_last, boxes, inner_idx, leaf_idx);
+	const int nc = gather_children(i, ch, width, leaf_max, wv, sorted_tri, left, right, range_first, range_last, boxes, inner_idx, leaf_idx);
 	uint32_t units = 0;
 	for (int k = 0; k < nc; ++k)
-		units += ch[k].leaf ? 2u : 1u;
+		units += child_units(ch[k]);
 	gsize[inner_idx[i]] = (units + 1u) & ~1u;
 }
 // 6b. where every record goes: the children of inner record i from unit 2 + gbase[i] on (units 0, 1 = the root record and its pad)
-__global__ void k_assign_units(int n, int width, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri, const int* __restrict__ left,
+__global__ void k_assign_units(int n, int width, int leaf_max, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri, const int* __restrict__ left,
 							   const int* __restrict__ right, const int* __restrict__ range_first, const int* __restrict__ range_last,
 							   const float* __restrict__ boxes, const uint32_t* __restrict__ inner_flag, const uint32_t* __restrict__ inner_idx,
 							   const uint32_t* __restrict__ leaf_idx, const uint32_t* __restrict__ gbase, uint32_t* __restrict__ inner_unit,
@@ -544,39 +585,42 @@ __global__ void k_assign_units(int n, int width, const float4* __restrict__ wv, 
 	if (i == 0)
 		inner_unit[inner_idx[0]] = 0u;
 	ChildRef ch[MAX_WIDE];
-	const int nc  = gather_children(i, ch, width, wv, sorted_tri, left, right, range_first, range_last, boxes, inner_idx, leaf_idx);
+	const int nc  = gather_children(i, ch, width, leaf_max, wv, sorted_tri, left, right, range_first, range_last, boxes, inner_idx, leaf_idx);
 	uint32_t unit = 2u + gbase[inner_idx[i]];
 	for (int k = 0; k < nc; ++k) {
 		if (ch[k].leaf)
-			leaf_unit[ch[k].id] = unit;
+			leaf_unit[ch[k].id] = unit | (ch[k].single ? LEAF_UNIT_SINGLE : 0u);
 		else
 			inner_unit[ch[k].id] = unit;
-		unit += ch[k].leaf ? 2u : 1u;
+		unit += child_units(ch[k]);
 	}
 }
 // 6c. the inner records
-__global__ void k_emit_inner(int n, int width, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri, const int* __restrict__ left,
+__global__ void k_emit_inner(int n, int width, int leaf_max, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri, const int* __restrict__ left,
 							 const int* __restrict__ right, const int* __restrict__ range_first, const int* __restrict__ range_last,
 							 const float* __restrict__ boxes, const uint32_t* __restrict__ inner_flag, const uint32_t* __restrict__ inner_idx,
 							 const uint32_t* __restrict__ leaf_idx, const uint32_t* __restrict__ gbase, const uint32_t* __restrict__ inner_unit,
-							 Rec64* __restrict__ recs)
+							 Rec64* __restrict__ recs, uint32_t* __restrict__ bad)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n - 1 || !inner_flag[i])
 		return;
 	ChildRef ch[MAX_WIDE];
-	const int nc = gather_children(i, ch, width, wv, sorted_tri, left, right, range_first, range_last, boxes, inner_idx, leaf_idx);
+	const int nc = gather_children(i, ch, width, leaf_max, wv, sorted_tri, left, right, range_first, range_last, boxes, inner_idx, leaf_idx);
 	uint32_t offs[MAX_WIDE] = { 0u, 0u, 0u, 0u, 0u, 0u }, off = 0u;
 	for (int k = 0; k < nc; ++k) {
 		offs[k] = off;
-		off += ch[k].leaf ? 2u : 1u;
+		off += child_units(ch[k]);
 	}
+	if (off - child_units(ch[nc - 1]) > 63u) // (six children of two units at most: never; a payload byte holds six offset bits)
+		atomicAdd(bad, 1u);
 	write_inner_q(recs + inner_unit[inner_idx[i]], ch, nc, 2u + gbase[inner_idx[i]], offs);
 }
 
 // 6d. self-check of the emitted structure, before any ray walks it (a bad child ref would be an out-of-bounds access in every tracing kernel):
-// every child of every inner record lies inside the array, leaves on even units with 1..3 triangles, inner children with sane exponents.
-__global__ void k_validate(uint32_t n_inner, const uint32_t* __restrict__ inner_unit, const Rec64* __restrict__ recs, uint32_t n_units, uint32_t* __restrict__ bad)
+// every child of every inner record lies inside the array, 128-byte leaves on even units with 1..3 triangles, single leaves with a triangle
+// of the scene and a zero tail, inner children with sane exponents.  (k_emit_inner counts a payload offset that overflows its six bits.)
+__global__ void k_validate(uint32_t n_inner, const uint32_t* __restrict__ inner_unit, const Rec64* __restrict__ recs, uint32_t n_units, uint32_t n_tris, uint32_t* __restrict__ bad)
 {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n_inner)
@@ -595,8 +639,14 @@ __global__ void k_validate(uint32_t n_inner, const uint32_t* __restrict__ inner_
 	}
 	for (int k = 0; k < MAX_WIDE && ok; ++k) {
 		const uint32_t ref = base + (((k < 4 ? pw : w[15]) >> (8 * (k & 3))) & 0xFFu), cu = ref >> REC_UNIT_SHIFT;
-		ok				   = ok && (ref & 2u) == 0u;
-		if (ref & REC_LEAF_BIT) {
+		ok				   = ok && ((ref & REC_SINGLE_BIT) == 0u || (ref & REC_LEAF_BIT) != 0u);
+		if (ok && (ref & REC_SINGLE_BIT)) { // a single leaf: one unit inside the array, a triangle of the scene without an analytic bit, a zero tail
+			ok = cu + 1u <= n_units;
+			if (ok) {
+				const uint32_t* c = reinterpret_cast<const uint32_t*>(recs + cu);
+				ok				  = c[9] < n_tris && (c[10] & ~0xFFu) == 0u && (c[11] | c[12] | c[13] | c[14] | c[15]) == 0u;
+			}
+		} else if (ref & REC_LEAF_BIT) {
 			ok = (cu & 1u) == 0u && cu + 2u <= n_units;
 			if (ok) {
 				const uint32_t cnt = reinterpret_cast<const uint32_t*>(recs + cu)[30];
@@ -654,15 +704,22 @@ __global__ void k_emit_leaves(uint32_t n, const float4* __restrict__ wv, const u
 		}
 		f[10 * k + 9] = __uint_as_float(t);
 	}
-	f[30]		= __uint_as_float(cnt);
-	f[31]		= __uint_as_float(classes); // material class of the triangle in slot k in byte k (the persistent kernel's shade queues bin by it)
-	float4* dst = reinterpret_cast<float4*>(recs + leaf_unit[leaf_idx[pos]]);
+	const uint32_t lu = leaf_unit[leaf_idx[pos]];
+	float4* dst		  = reinterpret_cast<float4*>(recs + (lu & ~LEAF_UNIT_SINGLE));
+	if (lu & LEAF_UNIT_SINGLE) { // single leaf (pr_device.h): the triangle, its index, its class; one unit and nothing past it
+		f[10] = __uint_as_float(classes & 0xFFu);
+		for (int q = 0; q < 4; ++q)
+			dst[q] = make_float4(f[4 * q], f[4 * q + 1], f[4 * q + 2], f[4 * q + 3]); // (floats 11..15 are zero: one triangle)
+		return;
+	}
+	f[30] = __uint_as_float(cnt);
+	f[31] = __uint_as_float(classes); // material class of the triangle in slot k in byte k (the persistent kernel's shade queues bin by it)
 	for (int q = 0; q < 8; ++q)
 		dst[q] = make_float4(f[4 * q], f[4 * q + 1], f[4 * q + 2], f[4 * q + 3]);
 }
 
-// tiny scenes (n <= 3): one inner record whose only child is the single leaf
-__global__ void k_tiny_scene(uint32_t n, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri, Rec64* __restrict__ recs, uint32_t* __restrict__ leaf_unit,
+// tiny scenes (n <= the leaf policy): one inner record whose only child is the only leaf -- under policy 1 a single leaf if it is a triangle
+__global__ void k_tiny_scene(uint32_t n, int leaf_max, const float4* __restrict__ wv, const uint32_t* __restrict__ sorted_tri, Rec64* __restrict__ recs, uint32_t* __restrict__ leaf_unit,
 							 const uint8_t* __restrict__ tri_class, const uint32_t* __restrict__ tri_entity, const DevEntity* __restrict__ entities)
 {
 	if (blockIdx.x != 0 || threadIdx.x != 0)
@@ -715,11 +772,17 @@ __global__ void k_tiny_scene(uint32_t n, const float4* __restrict__ wv, const ui
 		only.hi[a] = hi[a];
 	}
 	only.leaf			 = true;
+	only.single			 = leaf_max == 1 && wv[3 * sorted_tri[0]].w == 0.0f;
 	only.id				 = 0u;
 	const uint32_t off0[4] = { 0u, 0u, 0u, 0u };
 	write_inner_q(recs, &only, 1, 2u, off0);
-	leaf_unit[0] = 2u;
+	leaf_unit[0] = 2u | (only.single ? LEAF_UNIT_SINGLE : 0u);
 	float4* d1	 = reinterpret_cast<float4*>(recs + 2);
+	if (only.single) { // (units 2..3 were zeroed: the tail words and the pad unit stay zero)
+		leaf[10] = __uint_as_float(classes & 0xFFu);
+		leaf[30] = 0.0f;
+		leaf[31] = 0.0f;
+	}
 	for (int q = 0; q < 8; ++q)
 		d1[q] = make_float4(leaf[4 * q], leaf[4 * q + 1], leaf[4 * q + 2], leaf[4 * q + 3]);
 }
@@ -908,6 +971,14 @@ bool build_lbvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream
 	std::vector<uint32_t> codes[3]; // the sort key's entity field: ids, paths in a tree over the entities' boxes, or ranks in the Morton order of their centres
 	double best_cost = INFINITY, first_cost = INFINITY;
 	int best_order	 = 0;
+	// The leaf policy (BvhBuildInput::leaf).  `auto` builds the candidates of policy 1 first, then those of policy 3, prices the best tree of
+	// either (leaf_price) and -- only if policy 1 won by LEAF_MARGIN -- builds that one once more: where today's leaves stay, nothing is built twice.
+	const bool tiny		 = n <= (in.leaf == 1 ? 1u : 3u); // one record and one leaf (k_tiny_scene)
+	const bool leaf_auto = in.leaf == 0 && !tiny;
+	bool leaf_final		 = !leaf_auto;
+	int leaf_max		 = (leaf_auto || in.leaf == 1) ? 1 : 3;
+	double leaf_areas[2] = { 0.0, 0.0 }, root_area = 1.0, price[2] = { 0.0, 0.0 } /* policy 3, policy 1 */;
+	double* leaf_area_dev = nullptr;
 	out.recs	   = nullptr;
 	out.leaf_units = nullptr;
 	{
@@ -948,7 +1019,8 @@ bool build_lbvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream
 		}
 		HIPC(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, keys, keys_sorted, vals, vals_sorted, (int)n, 0, 64, stream));
 		HIPC(hipMalloc(&temp, temp_bytes));
-		if (n > 3) {
+		if (!tiny) {
+			HIPC(hipMalloc(&leaf_area_dev, sizeof(double) * 2));
 			HIPC(hipMalloc(&left, sizeof(int) * (n - 1)));
 			HIPC(hipMalloc(&right, sizeof(int) * (n - 1)));
 			HIPC(hipMalloc(&rf, sizeof(int) * (n - 1)));
@@ -972,14 +1044,17 @@ bool build_lbvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream
 				HIPC(hipMalloc(&front_count, sizeof(uint32_t)));
 			}
 		}
-		const bool top_forced = in.top >= 0 && in.top <= 2 && n > 3 && in.n_entities > 1; // (a forced top builds that order only)
-		const int n_orders	  = (n > 3 && in.n_entities > 1 && !top_forced) ? 3 : 1;
+		const bool top_forced = in.top >= 0 && in.top <= 2 && !tiny && in.n_entities > 1; // (a forced top builds that order only)
+		const int n_orders	  = (!tiny && in.n_entities > 1 && !top_forced) ? 3 : 1;
+		for (;;) { // the leaf policies
+		best_cost = first_cost = INFINITY;
+		best_order			   = 0;
 		for (int pass = 0, order = top_forced ? in.top : 0;; ++pass) {
 			HIPC(hipMemcpyAsync(entity_rank, codes[order].data(), codes[order].size() * 4, hipMemcpyHostToDevice, stream));
 			hipLaunchKernelGGL(k_morton, dim3(G), dim3(B), 0, stream, n, wv, in.tri_entity, ebounds, entity_rank, keys, vals);
 			HIPC(hipGetLastError());
 			HIPC(hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys, keys_sorted, vals, vals_sorted, (int)n, 0, 64, stream));
-			if (n <= 3)
+			if (tiny)
 				break;
 			width			= 0;
 			out.top			= order;
@@ -994,9 +1069,11 @@ bool build_lbvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream
 			HIPC(hipMemsetAsync(leaf_cnt, 0, sizeof(uint32_t) * n, stream));
 			HIPC(hipMemsetAsync(bounds_dev, 0, sizeof(uint32_t) * 3, stream));
 			HIPC(hipMemsetAsync(area_sums, 0, sizeof(double) * 3, stream));
+			HIPC(hipMemsetAsync(leaf_area_dev, 0, sizeof(double) * 2, stream));
 			hipLaunchKernelGGL(k_radix_tree, dim3(G), dim3(B), 0, stream, (int)n, keys_sorted, left, right, rf, rl, parent);
 			hipLaunchKernelGGL(k_fit_bounds, dim3(G), dim3(B), 0, stream, (int)n, wv, vals_sorted, left, right, parent, boxes, arrive);
-			hipLaunchKernelGGL(k_depth_and_flags, dim3(G), dim3(B), 0, stream, (int)n, parent, rf, rl, inner_flag, odd_flag, leaf_flag, leaf_cnt, bounds_dev);
+			hipLaunchKernelGGL(k_depth_and_flags, dim3(G), dim3(B), 0, stream, (int)n, parent, rf, rl, inner_flag, odd_flag, leaf_flag, leaf_cnt, bounds_dev,
+							   leaf_max, wv, vals_sorted, boxes, leaf_area_dev);
 			HIPC(hipGetLastError());
 			if (in.width != 4) { // the greedy collapse: which radix nodes are records follows top-down from the root, one launch per level
 				HIPC(hipMemsetAsync(stack_bound, 0, sizeof(uint32_t), stream)); // the root's
@@ -1008,7 +1085,7 @@ bool build_lbvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream
 				uint32_t n_front = 1u;
 				while (n_front != 0u) {
 					HIPC(hipMemsetAsync(front_count, 0, sizeof(uint32_t), stream));
-					hipLaunchKernelGGL(k_mark_records, dim3((n_front + B - 1) / B), dim3(B), 0, stream, (int)n_front, front, MAX_WIDE, wv, vals_sorted, left, right, rf, rl, boxes,
+					hipLaunchKernelGGL(k_mark_records, dim3((n_front + B - 1) / B), dim3(B), 0, stream, (int)n_front, front, MAX_WIDE, leaf_max, wv, vals_sorted, left, right, rf, rl, boxes,
 									   greedy_flag, front_next, front_count, stack_bound, bounds_dev + 2);
 					HIPC(hipMemcpyAsync(&n_front, front_count, 4, hipMemcpyDeviceToHost, stream));
 					HIPC(hipStreamSynchronize(stream));
@@ -1025,10 +1102,12 @@ bool build_lbvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream
 				hipLaunchKernelGGL(k_area_sum, dim3(G), dim3(B), 0, stream, (int)n, odd_flag, boxes, area_sums + 1);
 				HIPC(hipMemcpyAsync(bounds_host, bounds_dev, sizeof(bounds_host), hipMemcpyDeviceToHost, stream));
 				HIPC(hipMemcpyAsync(sums, area_sums, sizeof(sums), hipMemcpyDeviceToHost, stream));
+				HIPC(hipMemcpyAsync(leaf_areas, leaf_area_dev, sizeof(leaf_areas), hipMemcpyDeviceToHost, stream));
 				HIPC(hipMemcpyAsync(root_box, boxes, sizeof(root_box), hipMemcpyDeviceToHost, stream));
 				HIPC(hipStreamSynchronize(stream));
 				const double rx = (double)root_box[3] - root_box[0], ry = (double)root_box[4] - root_box[1], rz = (double)root_box[5] - root_box[2];
 				const double ra = std::max(rx * ry + ry * rz + rz * rx, 1e-300);
+				root_area		= ra;
 				// the two parity collapses differ in where every subtree's records start: which is the better one is luck of the scene's layout
 				// (C4: 3.9 % more inner records per ray with the wrong one), so both are priced
 				const uint32_t bound_even = 3u * (bounds_host[0] + 1u), bound_odd = 3u * (bounds_host[1] + 1u), bound6 = bounds_host[2];
@@ -1036,7 +1115,7 @@ bool build_lbvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream
 				// (a forced parity is taken whether it fits or not: a tree that does not fit is refused, as for a forced width)
 				const bool odd = in.parity >= 0 ? in.parity == 1 : fit_odd && (!fit_even || sums[1] < sums[0]);
 				const uint32_t bound4 = odd ? bound_odd : bound_even;
-				if (in.parity >= 0 && in.width != 6 && bound4 > in.stack_capacity) { // (not left to `auto`'s way out, the six-wide tree: the caller asked for THIS tree)
+				if (in.parity >= 0 && in.width != 6 && bound4 > in.stack_capacity && leaf_final) { // (an `auto` leaf policy's trial that does not fit is priced out below; not left to `auto`'s way out, the six-wide tree: the caller asked for THIS tree)
 					err = "the four-wide BVH of the forced parity is " + std::to_string(bound4) + " stack entries deep in the worst case, the traversal stack holds "
 						  + std::to_string(in.stack_capacity);
 					goto done;
@@ -1082,14 +1161,40 @@ bool build_lbvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream
 				break;
 			}
 		}
-		if (n <= 3) {
+		if (tiny)
+			break;
+		{ // the price of the tree just built (the best of this policy): expected records of each kind per ray through the scene's box, weighted
+			out.leaf	  = leaf_max;
+			out.visits[0] = out.wide ? out.cost6 : out.cost4;
+			out.visits[1] = (float)(leaf_areas[0] / root_area);
+			out.visits[2] = (float)(leaf_areas[1] / root_area);
+			const double p = out.stack_bound > in.stack_capacity
+								 ? INFINITY
+								 : (double)out.visits[0] * (out.wide ? WIDE_STEP_COST : 1.0) + (double)out.visits[1] * LEAF3_STEP_COST + (double)out.visits[2] * LEAF1_STEP_COST;
+			price[leaf_max == 1 ? 1 : 0] = p;
+			if (leaf_final)
+				break;
+			if (leaf_max == 1) { // `auto`: policy 1 is priced, now today's leaves
+				leaf_max = 3;
+				continue;
+			}
+			leaf_final = true;
+			if (!(price[1] < LEAF_MARGIN * price[0])) // (also when neither fits: today's refusal below)
+				break;
+			leaf_max = 1;
+		}
+		}
+		out.price3 = std::isfinite(price[0]) ? (float)price[0] : 0.0f;
+		out.price1 = std::isfinite(price[1]) ? (float)price[1] : 0.0f;
+		if (tiny) {
 			HIPC(hipMalloc(&out.recs, sizeof(Rec64) * 4));
 			HIPC(hipMemsetAsync(out.recs, 0, sizeof(Rec64) * 4, stream));
 			HIPC(hipMalloc(&out.leaf_units, sizeof(uint32_t)));
-			hipLaunchKernelGGL(k_tiny_scene, dim3(1), dim3(64), 0, stream, n, wv, vals_sorted, out.recs, out.leaf_units, in.tri_class, in.tri_entity, in.entities);
+			hipLaunchKernelGGL(k_tiny_scene, dim3(1), dim3(64), 0, stream, n, leaf_max, wv, vals_sorted, out.recs, out.leaf_units, in.tri_class, in.tri_entity, in.entities);
 			out.n_inner = 1;
 			out.n_leaf	= 1;
 			out.n_units = 4;
+			out.leaf	= leaf_max;
 		} else {
 			HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, t2a, inner_flag, inner_idx, (int)n, stream));
 			HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, t2b, leaf_flag, leaf_idx, (int)n, stream));
@@ -1117,7 +1222,7 @@ bool build_lbvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream
 			HIPC(hipMalloc(&inner_unit, sizeof(uint32_t) * std::max<size_t>(out.n_inner, 1)));
 			HIPC(hipMalloc(&out.leaf_units, sizeof(uint32_t) * std::max<size_t>(out.n_leaf, 1)));
 			HIPC(hipMemsetAsync(gsize, 0, sizeof(uint32_t) * (size_t(out.n_inner) + 1), stream));
-			hipLaunchKernelGGL(k_group_sizes, dim3(G), dim3(B), 0, stream, (int)n, width, wv, vals_sorted, left, right, rf, rl, boxes, inner_flag, inner_idx, leaf_idx, gsize);
+			hipLaunchKernelGGL(k_group_sizes, dim3(G), dim3(B), 0, stream, (int)n, width, leaf_max, wv, vals_sorted, left, right, rf, rl, boxes, inner_flag, inner_idx, leaf_idx, gsize);
 			HIPC(hipGetLastError());
 			{
 				size_t t3 = 0;
@@ -1140,16 +1245,16 @@ bool build_lbvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream
 			}
 			HIPC(hipMalloc(&out.recs, sizeof(Rec64) * size_t(out.n_units)));
 			HIPC(hipMemsetAsync(out.recs, 0, sizeof(Rec64) * size_t(out.n_units), stream));
-			hipLaunchKernelGGL(k_assign_units, dim3(G), dim3(B), 0, stream, (int)n, width, wv, vals_sorted, left, right, rf, rl, boxes, inner_flag, inner_idx, leaf_idx, gbase,
+			HIPC(hipMemsetAsync(gsize, 0, sizeof(uint32_t), stream)); // gsize is free again: its first word takes the count of bad records (k_emit_inner, k_validate)
+			hipLaunchKernelGGL(k_assign_units, dim3(G), dim3(B), 0, stream, (int)n, width, leaf_max, wv, vals_sorted, left, right, rf, rl, boxes, inner_flag, inner_idx, leaf_idx, gbase,
 							   inner_unit, out.leaf_units);
-			hipLaunchKernelGGL(k_emit_inner, dim3(G), dim3(B), 0, stream, (int)n, width, wv, vals_sorted, left, right, rf, rl, boxes, inner_flag, inner_idx, leaf_idx, gbase,
-							   inner_unit, out.recs);
+			hipLaunchKernelGGL(k_emit_inner, dim3(G), dim3(B), 0, stream, (int)n, width, leaf_max, wv, vals_sorted, left, right, rf, rl, boxes, inner_flag, inner_idx, leaf_idx, gbase,
+							   inner_unit, out.recs, gsize);
 			hipLaunchKernelGGL(k_emit_leaves, dim3(G), dim3(B), 0, stream, n, wv, vals_sorted, leaf_flag, leaf_cnt, leaf_idx, out.leaf_units, out.recs, in.tri_class, in.tri_entity, in.entities);
 			HIPC(hipGetLastError());
-			{ // gsize is free again: its first word takes the count of bad records
+			{
 				uint32_t bad = 0;
-				HIPC(hipMemsetAsync(gsize, 0, sizeof(uint32_t), stream));
-				hipLaunchKernelGGL(k_validate, dim3((out.n_inner + B - 1) / B), dim3(B), 0, stream, out.n_inner, inner_unit, out.recs, out.n_units, gsize);
+				hipLaunchKernelGGL(k_validate, dim3((out.n_inner + B - 1) / B), dim3(B), 0, stream, out.n_inner, inner_unit, out.recs, out.n_units, n, gsize);
 				HIPC(hipMemcpyAsync(&bad, gsize, 4, hipMemcpyDeviceToHost, stream));
 				HIPC(hipStreamSynchronize(stream));
 				if (bad != 0u) {
@@ -1167,7 +1272,7 @@ done:
 	(void)hipFree(left); (void)hipFree(right); (void)hipFree(rf); (void)hipFree(rl); (void)hipFree(parent); (void)hipFree(boxes); (void)hipFree(arrive);
 	(void)hipFree(inner_flag); (void)hipFree(inner_idx); (void)hipFree(leaf_flag); (void)hipFree(leaf_cnt); (void)hipFree(leaf_idx);
 	(void)hipFree(front); (void)hipFree(front_next); (void)hipFree(front_count); (void)hipFree(area_sums); (void)hipFree(greedy_flag); (void)hipFree(stack_bound); (void)hipFree(bounds_dev); (void)hipFree(odd_flag);
-	(void)hipFree(temp); (void)hipFree(temp2); (void)hipFree(gsize); (void)hipFree(gbase); (void)hipFree(inner_unit);
+	(void)hipFree(temp); (void)hipFree(temp2); (void)hipFree(gsize); (void)hipFree(gbase); (void)hipFree(inner_unit); (void)hipFree(leaf_area_dev);
 	if (!ok) {
 		(void)hipFree(out.recs);
 		(void)hipFree(out.leaf_units);

@@ -121,7 +121,7 @@ __device__ __forceinline__ void path_wave(const DevScene& sc, const PathState& p
 	sh_tail[QR]	  = S;
 	uint32_t live = S;	  // slots that still own, or may still acquire, a pixel
 
-	uint32_t cn_c = 0, cl_c = 0, cn_a = 0, cl_a = 0, witers = 0, sbatches = 0, slanes = 0;
+	uint32_t cn_c = 0, cl_c = 0, cn_a = 0, cl_a = 0, cs_c = 0, cs_a = 0, witers = 0, sbatches = 0, slanes = 0;
 	unsigned long long t_shade = 0;
 	const unsigned long long t_start = COUNT ? wall_clock64() : 0ull;
 
@@ -285,10 +285,21 @@ __device__ __forceinline__ void path_wave(const DevScene& sc, const PathState& p
 					}
 					trav_inner_rec<MODE_MIXED>(s, st, q0, q1, q2, qw, wide, top);
 				} else {
-					const float4 q3 = rec[3], q4 = rec[4], q5 = rec[5], q6 = rec[6], q7 = rec[7];
+					float4 q3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q4 = q3, q5 = q3, q6 = q3, q7 = q3;
+					if (!(s.cur & REC_SINGLE_BIT)) { // (a single leaf ends with q0..q2)
+						q3 = rec[3];
+						q4 = rec[4];
+						q5 = rec[5];
+						q6 = rec[6];
+						q7 = rec[7];
+					}
 					if (COUNT) {
 						cl_c += s.any ? 0 : 1;
 						cl_a += s.any ? 1 : 0;
+						if (s.cur & REC_SINGLE_BIT) {
+							cs_c += s.any ? 0 : 1;
+							cs_a += s.any ? 1 : 0;
+						}
 					}
 					trav_leaf_rec<MODE_MIXED, (FEATS & ANA_ALL), (NQ > 1)>(s, st, q0, q1, q2, q3, q4, q5, q6, q7, top);
 				}
@@ -349,6 +360,10 @@ __device__ __forceinline__ void path_wave(const DevScene& sc, const PathState& p
 			atomicAdd(&a.gstats[CNT_NODES_ANY], (unsigned long long)cn_a);
 		if (cl_a)
 			atomicAdd(&a.gstats[CNT_TRIS_ANY], (unsigned long long)cl_a);
+		if (cs_c)
+			atomicAdd(&a.gstats[CNT_SINGLES_CLOSEST], (unsigned long long)cs_c);
+		if (cs_a)
+			atomicAdd(&a.gstats[CNT_SINGLES_ANY], (unsigned long long)cs_a);
 		if (witers)
 			atomicAdd(&a.gstats[CNT_WAVE_ITERS_CLOSEST], (unsigned long long)witers);
 		if (sbatches) {

@@ -59,14 +59,22 @@ constexpr float CIE_Y_NORM	   = CIE_Y_NORM_SUM * CIE_DELTA;
 //          pays for the fused one-fma-per-plane slab arithmetic of the traversal step.
 //   leaf  (two units, 128 B = one L2 line, 128-byte aligned): triangle k (k < 3) in floats [10k, 10k+10) = v0, v1, v2
 //          (world space), original triangle index; float 30 = triangle count, float 31 = material classes
-// child ref: 4 * unit index | REC_LEAF_BIT for leaves (a record's address is base + 16 * (ref & ~3): one v_lshl_add_u64); REC_EMPTY = no record.
+//   single leaf (one unit, 64-byte aligned): ONE triangle -- floats 0..8 = v0, v1, v2
+//          (world space), float 9 = original triangle index (a triangle only: no sphere or disk bit), float 10 = material class in its
+//          low byte, floats 11..15 = zero.  A step on it reads nothing past its 64 bytes.  Analytic primitives keep the 128-byte leaf.
+//          (the builder's leaf policy 1, bvh.hip: every triangle a single leaf; policy 3, today's default, builds none)
+//          The children of a record lie in the order 128-byte leaves, single leaves, inner records.
+// child ref: 4 * unit index | REC_LEAF_BIT for leaves, | REC_SINGLE_BIT as well for single leaves (a record's address is
+// base + 16 * (ref & ~3): one v_lshl_add_u64); REC_EMPTY = no record (it carries both bits: the stepping loops keep finished lanes out of a step).
 struct __attribute__((aligned(64))) Rec64 {
 	float4 q[4];
 };
 static_assert(sizeof(Rec64) == 64, "Rec64 must be 64 bytes");
 constexpr uint32_t REC_LEAF_BIT = 1u;
+constexpr uint32_t REC_SINGLE_BIT = 2u; // with REC_LEAF_BIT: a single leaf
 constexpr uint32_t REC_EMPTY	= 0xFFFFFFFFu;
-constexpr uint32_t REC_UNIT_SHIFT = 2u; // ref = unit << 2 | leaf bit
+constexpr uint32_t REC_UNIT_SHIFT = 2u; // ref = unit << 2 | single bit | leaf bit
+constexpr uint32_t LEAF_UNIT_SINGLE = 0x80000000u;		   // BvhBuildOutput::leaf_units: the leaf at this unit is a single leaf
 // the record a ref names (ref & ~3 = 4 * unit, 16 bytes per quarter unit)
 __host__ __device__ __forceinline__ const float4* rec_ptr(const Rec64* recs, uint32_t ref)
 {

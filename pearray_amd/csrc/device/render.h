@@ -5,7 +5,7 @@
 namespace prd {
 // gstats: PRGPU_STAT_COUNT statistics, then inner/leaf record counters of closest and any-hit traversal, then wave-iteration
 // counters, then the persistent kernel's shading passes / shaded vertices / time split
-constexpr int N_DEVICE_COUNTERS = PRGPU_STAT_COUNT + 30; // ... + diagnostics (PRGPU_DEBUG_COUNTERS): leaf-step / inner-step ticks, shader cycles, refill ticks, ray-end ticks
+constexpr int N_DEVICE_COUNTERS = PRGPU_STAT_COUNT + 32; // ... + diagnostics (PRGPU_DEBUG_COUNTERS): leaf-step / inner-step ticks, shader cycles, refill ticks, ray-end ticks
 
 // Scratch of one persistent traversal launch: queue head (u32) and the per-thread stack spill slab.
 // Launches that may run concurrently need separate workspaces.
@@ -168,7 +168,7 @@ void launch_service_closest(const DevScene& sc, uint32_t n, const float* org, co
 void launch_tri_slot(const DevScene& sc, const uint32_t* leaf_units /* unit of every leaf record (BvhBuildOutput) */, uint32_t* tri_slot, hipStream_t st); // fills DevScene::tri_slot from the leaf records
 void launch_service_closest_split(const DevScene& sc, uint32_t n, const float* org, const float* dir, const float* tmin, const float* tmax,
 								  uint32_t* entity, uint32_t* prim, float* u, float* v, float* t, const TraceWorkspace& ws, uint32_t* tri_slot,
-								  unsigned long long* gstats, hipStream_t st); // prototype, see render.hip
+								  unsigned long long* gstats, bool leaf_single /* the tree's leaves are single leaves */, hipStream_t st); // prototype, see render.hip
 void launch_service_any(const DevScene& sc, uint32_t n, const float* org, const float* dir, const float* tmin, const float* distance,
 						uint8_t* occluded, const TraceWorkspace& ws, unsigned long long* gstats, hipStream_t st);
 // What prgpu_enable_ambient_occlusion allocates; passed by value.

@@ -48,7 +48,8 @@ struct Hit {
 
 // indices into the extra device counters after the 11 statistics
 enum { CNT_NODES_CLOSEST = PRGPU_STAT_COUNT, CNT_TRIS_CLOSEST, CNT_NODES_ANY, CNT_TRIS_ANY, CNT_WAVE_ITERS_CLOSEST, CNT_WAVE_ITERS_ANY, CNT_SHADE_BATCHES, CNT_SHADE_LANES, CNT_SHADE_TICKS, CNT_IDLE_TICKS, CNT_TOTAL_TICKS, CNT_LEAF_TICKS, CNT_INNER_TICKS, CNT_TOTAL_CYCLES, CNT_REFILL_TICKS, CNT_FIN_TICKS, CNT_CAMERA_TICKS, CNT_VERTEX_TICKS,
-	   CNT_CLS_TICKS0, CNT_CLS_BATCHES0 = CNT_CLS_TICKS0 + 4, CNT_CLS_LANES0 = CNT_CLS_BATCHES0 + 4 }; // per shade queue (material classes, then ended paths): pass time, passes, lanes
+	   CNT_CLS_TICKS0, CNT_CLS_BATCHES0 = CNT_CLS_TICKS0 + 4, CNT_CLS_LANES0 = CNT_CLS_BATCHES0 + 4, // per shade queue (material classes, then ended paths): pass time, passes, lanes
+	   CNT_SINGLES_CLOSEST = CNT_CLS_LANES0 + 4, CNT_SINGLES_ANY }; // how many of CNT_TRIS_* were single leaves
 
 // ---- traversal ------------------------------------------------------------------------------------------------
 // Persistent waves pull rays from a queue head (one atomic per wave refill), walk the 4-wide BVH one
@@ -272,7 +273,8 @@ __device__ __forceinline__ void trav_inner(const DevScene& sc, Trav& s, Stack& s
 	trav_inner_rec<M>(s, st, q0, q1, q2, q3, wide, &top);
 }
 
-// Leaf step: fetch the leaf record (<= 3 triangles) and run the watertight test on each.
+// Leaf step: fetch the leaf record (<= 3 triangles, or a single leaf's one: s.cur carries REC_SINGLE_BIT, the caller has loaded q0..q2 only and
+// passes zeros for the rest) and run the watertight test on each.
 // ANA: FEAT_SPHERES and / or FEAT_DISKS -- the leaf may hold analytic spheres / disks (scenes with such entities); compiled out of the
 // persistent kernel's variants that do not carry the feature
 constexpr uint32_t ANA_ALL = FEAT_SPHERES | FEAT_DISKS;
@@ -283,10 +285,11 @@ __device__ __forceinline__ void leaf_test(Trav& s, const float4& q0, const float
 	const bool ANY = M == MODE_ANY || (M == MODE_MIXED && s.any);
 	const float f[32] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w,
 						  q4.x, q4.y, q4.z, q4.w, q5.x, q5.y, q5.z, q5.w, q6.x, q6.y, q6.z, q6.w, q7.x, q7.y, q7.z, q7.w };
-	const uint32_t count = __float_as_uint(f[30]);
+	const bool single	 = (s.cur & REC_SINGLE_BIT) != 0u;
+	const uint32_t count = single ? 1u : __float_as_uint(f[30]);
 #pragma unroll
 	for (int k = 0; k < 3; ++k) {
-		if ((uint32_t)k < count) {
+		if ((uint32_t)k < count) { // (tests 2 and 3: skipped by the wave when no lane holds such a leaf)
 			float t, u, v;
 			const uint32_t prim = __float_as_uint(f[10 * k + 9]);
 			bool hit;
@@ -309,7 +312,7 @@ __device__ __forceinline__ void leaf_test(Trav& s, const float4& q0, const float
 				} else if (t < s.best.t || (t == s.best.t && tri < s.best.tri)) {
 					s.best = Hit{ t, u, v, tri };
 					if (CLS)
-						s.cls = (__float_as_uint(f[31]) >> (8 * k)) & 0xFFu;
+						s.cls = k == 0 ? __float_as_uint(single ? f[10] : f[31]) & 0xFFu : (__float_as_uint(f[31]) >> (8 * k)) & 0xFFu;
 				}
 			}
 		}
@@ -332,7 +335,15 @@ template <int M>
 __device__ __forceinline__ void trav_leaf(const DevScene& sc, Trav& s, Stack& st)
 {
 	const float4* __restrict__ rec = rec_ptr(sc.recs, s.cur);
-	const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4], q5 = rec[5], q6 = rec[6], q7 = rec[7];
+	const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2];
+	float4 q3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q4 = q3, q5 = q3, q6 = q3, q7 = q3;
+	if (!(s.cur & REC_SINGLE_BIT)) { // a single leaf ends with its 64 bytes
+		q3 = rec[3];
+		q4 = rec[4];
+		q5 = rec[5];
+		q6 = rec[6];
+		q7 = rec[7];
+	}
 	const uint2 top = st.peek();
 	trav_leaf_rec<M, ANA_ALL>(s, st, q0, q1, q2, q3, q4, q5, q6, q7, &top);
 }
@@ -374,7 +385,7 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, uint32_t n_
 	uint32_t my_ray	   = 0;
 	bool has_ray	   = false;
 	bool exhausted	   = false; // wave-uniform: the queue has no more rays
-	uint32_t cn = 0, cl = 0, witers = 0;
+	uint32_t cn = 0, cl = 0, cs = 0, witers = 0;
 	const uint32_t lane = threadIdx.x & 63u;
 	for (;;) {
 		if (!exhausted) {
@@ -420,8 +431,10 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, uint32_t n_
 						++cn;
 					trav_inner<ANY>(sc, s, st);
 				} else {
-					if (COUNT)
+					if (COUNT) {
 						++cl;
+						cs += (s.cur & REC_SINGLE_BIT) ? 1u : 0u;
+					}
 					trav_leaf<ANY>(sc, s, st);
 				}
 			}
@@ -442,6 +455,8 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, uint32_t n_
 			atomicAdd(&gstats[ANY ? CNT_NODES_ANY : CNT_NODES_CLOSEST], (unsigned long long)cn);
 		if (cl)
 			atomicAdd(&gstats[ANY ? CNT_TRIS_ANY : CNT_TRIS_CLOSEST], (unsigned long long)cl);
+		if (cs)
+			atomicAdd(&gstats[ANY ? CNT_SINGLES_ANY : CNT_SINGLES_CLOSEST], (unsigned long long)cs);
 		if (witers)
 			atomicAdd(&gstats[ANY ? CNT_WAVE_ITERS_ANY : CNT_WAVE_ITERS_CLOSEST], (unsigned long long)witers);
 	}
@@ -2720,7 +2735,7 @@ __device__ __forceinline__ void path_persistent(const DevScene& sc, const PathSt
 
 	uint32_t spins	  = 0;
 	unsigned long long t_idle_since = 0;
-	uint32_t cn_c = 0, cl_c = 0, cn_a = 0, cl_a = 0, witers = 0, wleaf = 0, sbatches = 0, slanes = 0;
+	uint32_t cn_c = 0, cl_c = 0, cn_a = 0, cl_a = 0, cs_c = 0, cs_a = 0, witers = 0, wleaf = 0, sbatches = 0, slanes = 0;
 	unsigned long long t_shade = 0, t_idle = 0, t_leaf = 0, t_inner = 0, t_refill = 0, t_fin = 0, t_cam = 0, t_vert = 0;
 	unsigned long long t_cls[4] = { 0, 0, 0, 0 };
 	uint32_t b_cls[4] = { 0, 0, 0, 0 }, l_cls[4] = { 0, 0, 0, 0 };
@@ -3067,10 +3082,21 @@ __device__ __forceinline__ void path_persistent(const DevScene& sc, const PathSt
 					}
 					trav_inner_rec<MODE_MIXED>(s, st, q0, q1, q2, qw, wide, top);
 				} else {
-					const float4 q3 = rec[3], q4 = rec[4], q5 = rec[5], q6 = rec[6], q7 = rec[7];
+					float4 q3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q4 = q3, q5 = q3, q6 = q3, q7 = q3;
+					if (!(s.cur & REC_SINGLE_BIT)) { // the rest of a 128-byte leaf; a single leaf ends with q0..q2 (its fourth quarter is zero and is not read)
+						q3 = rec[3];
+						q4 = rec[4];
+						q5 = rec[5];
+						q6 = rec[6];
+						q7 = rec[7];
+					}
 					if (COUNT) {
 						cl_c += s.any ? 0 : 1;
 						cl_a += s.any ? 1 : 0;
+						if (s.cur & REC_SINGLE_BIT) {
+							cs_c += s.any ? 0 : 1;
+							cs_a += s.any ? 1 : 0;
+						}
 					}
 					trav_leaf_rec<MODE_MIXED, (FEATS & ANA_ALL), (NQ > 1)>(s, st, q0, q1, q2, q3, q4, q5, q6, q7, top);
 				}
@@ -3159,6 +3185,10 @@ __device__ __forceinline__ void path_persistent(const DevScene& sc, const PathSt
 			atomicAdd(&a.gstats[CNT_NODES_ANY], (unsigned long long)cn_a);
 		if (cl_a)
 			atomicAdd(&a.gstats[CNT_TRIS_ANY], (unsigned long long)cl_a);
+		if (cs_c)
+			atomicAdd(&a.gstats[CNT_SINGLES_CLOSEST], (unsigned long long)cs_c);
+		if (cs_a)
+			atomicAdd(&a.gstats[CNT_SINGLES_ANY], (unsigned long long)cs_a);
 		if (witers)
 			atomicAdd(&a.gstats[CNT_WAVE_ITERS_CLOSEST], (unsigned long long)witers);
 		if (wleaf) // split traversal: leaf batches (the steps above include them)
@@ -3330,7 +3360,7 @@ __device__ __forceinline__ void trav_inner_split(Trav& s, STK& st, const float4&
 				__hip_atomic_fetch_add(pending_own, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 #pragma unroll
 			for (int k = 0; k < NW; ++k)
-				if (lf[k]) // task = leaf unit << 8 | owner lane (the ref is unit << 2 | 1)
+				if (lf[k]) // task = leaf unit << 8 | owner lane (the ref is unit << 2 | leaf bits; the leaf kind is one per scene here: no analytic leaves)
 					__hip_atomic_store(&q[(pos++) & (SQ - 1u)], (((base + (key[k] & 0xFFu)) >> REC_UNIT_SHIFT) << 8) | tid, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 		}
 	}
@@ -3358,9 +3388,9 @@ __global__ void k_tri_slot(DevScene sc, const uint32_t* __restrict__ leaf_units,
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= sc.n_leaf)
 		return;
-	const uint32_t unit = leaf_units[i];
+	const uint32_t unit = leaf_units[i] & ~LEAF_UNIT_SINGLE;
 	const float* f		= reinterpret_cast<const float*>(sc.recs + unit);
-	const uint32_t cnt	= __float_as_uint(f[30]);
+	const uint32_t cnt	= (leaf_units[i] & LEAF_UNIT_SINGLE) ? 1u : __float_as_uint(f[30]);
 	for (uint32_t k = 0; k < cnt && k < 3u; ++k)
 		tri_slot[__float_as_uint(f[10 * k + 9]) & PRIM_INDEX_MASK] = (unit << 2) | k;
 }
@@ -3368,7 +3398,7 @@ template <bool WIDE>
 __global__ void __launch_bounds__(TRAV_BLOCK) k_service_closest_split(DevScene sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,
 																	 const float* __restrict__ tmin_a, const float* __restrict__ tmax_a, uint32_t* entity,
 																	 uint32_t* prim, float* u, float* v, float* t, uint32_t* queue_head, uint2* spill,
-																	 const uint32_t* __restrict__ tri_slot, int refill_below, unsigned long long* gstats)
+																	 const uint32_t* __restrict__ tri_slot, int refill_below, unsigned long long* gstats, bool leaf_single)
 {
 	constexpr uint32_t SQ = SplitRing<WIDE>::N;
 	__shared__ SplitShared<WIDE> sh;
@@ -3413,10 +3443,18 @@ __global__ void __launch_bounds__(TRAV_BLOCK) k_service_closest_split(DevScene s
 			r.Sz			  = rb.z;
 			const float tmin  = rb.w;
 			const float4* __restrict__ rec = reinterpret_cast<const float4*>(sc.recs + unit);
-			const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4], q5 = rec[5], q6 = rec[6], q7 = rec[7];
+			const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2];
+			float4 q3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q4 = q3, q5 = q3, q6 = q3, q7 = q3;
+			if (!leaf_single) { // (a tree of single leaves -- the split service runs triangle-only scenes: one kind per tree -- ends a leaf with q0..q2)
+				q3 = rec[3];
+				q4 = rec[4];
+				q5 = rec[5];
+				q6 = rec[6];
+				q7 = rec[7];
+			}
 			const float f[32] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w,
 								  q4.x, q4.y, q4.z, q4.w, q5.x, q5.y, q5.z, q5.w, q6.x, q6.y, q6.z, q6.w, q7.x, q7.y, q7.z, q7.w };
-			const uint32_t count = __float_as_uint(f[30]);
+			const uint32_t count = leaf_single ? 1u : __float_as_uint(f[30]);
 			unsigned long long key = ~0ull;
 #pragma unroll
 			for (int k = 0; k < 3; ++k) {
@@ -3532,6 +3570,8 @@ __global__ void __launch_bounds__(TRAV_BLOCK) k_service_closest_split(DevScene s
 		atomicAdd(&gstats[CNT_NODES_CLOSEST], (unsigned long long)cn);
 	if (cl)
 		atomicAdd(&gstats[CNT_TRIS_CLOSEST], (unsigned long long)cl);
+	if (cl && leaf_single)
+		atomicAdd(&gstats[CNT_SINGLES_CLOSEST], (unsigned long long)cl);
 	if (witers)
 		atomicAdd(&gstats[CNT_WAVE_ITERS_CLOSEST], (unsigned long long)witers);
 }
@@ -3651,15 +3691,15 @@ void launch_tri_slot(const DevScene& sc, const uint32_t* leaf_units, uint32_t* t
 }
 void launch_service_closest_split(const DevScene& sc, uint32_t n, const float* org, const float* dir, const float* tmin, const float* tmax,
 								  uint32_t* entity, uint32_t* prim, float* u, float* v, float* t, const TraceWorkspace& ws, uint32_t* tri_slot,
-								  unsigned long long* gstats, hipStream_t st)
+								  unsigned long long* gstats, bool leaf_single, hipStream_t st)
 {
 	(void)hipMemsetAsync(ws.queue_head, 0, sizeof(uint32_t), st);
 	if (sc.bvh_wide)
 		hipLaunchKernelGGL(k_service_closest_split<true>, trav_grid(ws, n), dim3(TRAV_BLOCK), 0, st, sc, n, org, dir, tmin, tmax, entity, prim, u, v, t, ws.queue_head,
-						   ws.spill, tri_slot, ws.refill_below, gstats);
+						   ws.spill, tri_slot, ws.refill_below, gstats, leaf_single);
 	else
 		hipLaunchKernelGGL(k_service_closest_split<false>, trav_grid(ws, n), dim3(TRAV_BLOCK), 0, st, sc, n, org, dir, tmin, tmax, entity, prim, u, v, t, ws.queue_head,
-						   ws.spill, tri_slot, ws.refill_below, gstats);
+						   ws.spill, tri_slot, ws.refill_below, gstats, leaf_single);
 }
 void launch_service_any(const DevScene& sc, uint32_t n, const float* org, const float* dir, const float* tmin, const float* distance,
 						uint8_t* occluded, const TraceWorkspace& ws, unsigned long long* gstats, hipStream_t st)

@@ -73,9 +73,10 @@ struct Knobs {
 	int bvh_width			   = 0;		  // PRGPU_BVH_WIDTH=auto|4|6: children per inner BVH record (0 = auto: the tree whose estimated cost is lower, device/bvh.hip)
 	int bvh_top				   = -1;	  // PRGPU_BVH_TOP=auto|file|area|morton: the order of the entities at the top of the tree (0 / 1 / 2; -1 = auto: all three are built, the cheapest
 										  // is kept).  A scene of one entity has no top to choose: prgpu_pipeline_info's bvh_top says what was built.
+	int bvh_leaf			   = 0;		  // PRGPU_BVH_LEAF=auto|3|1: the leaves of the BVH (3: 128-byte leaves of up to three triangles; 1: every triangle a single 64-byte leaf;
+									  // 0 = auto: both are built and priced, single leaves are kept where their price is lower by the margin device/bvh.hip states)
 	int bvh_parity			   = -1;	  // PRGPU_BVH_PARITY=auto|even|odd: which depths of the radix tree become four-wide records (0 / 1; -1 = auto: the cheaper one that fits the stack).
 										  // Test aids: the trees `auto` would not pick for a scene are walked on purpose (tests/test_gpu_bvh_width.py); no effect on a six-wide tree.
-	int trace_ranges		   = -1;	  // PRGPU_TRACE_RANGES=1: load the roctx library for the named ranges even when no profiler brought it along; 0: never emit ranges
 };
 Knobs read_knobs()
 {
@@ -98,6 +99,7 @@ Knobs read_knobs()
 	k.pp_kernel	 = choice("PRGPU_PP_KERNEL", { { "auto", 0 }, { "throughput", 1 }, { "latency", 2 } }, k.pp_kernel);
 	k.bvh_width	 = choice("PRGPU_BVH_WIDTH", { { "auto", 0 }, { "4", 4 }, { "6", 6 } }, k.bvh_width);
 	k.bvh_top	 = choice("PRGPU_BVH_TOP", { { "auto", -1 }, { "file", 0 }, { "area", 1 }, { "morton", 2 } }, k.bvh_top);
+	k.bvh_leaf	 = choice("PRGPU_BVH_LEAF", { { "auto", 0 }, { "3", 3 }, { "1", 1 } }, k.bvh_leaf);
 	k.bvh_parity = choice("PRGPU_BVH_PARITY", { { "auto", -1 }, { "even", 0 }, { "odd", 1 } }, k.bvh_parity);
 	k.pl.slots_per_wave	  = (uint32_t)num("PRGPU_PL_SLOTS", k.pl.slots_per_wave, 64, 256);
 	k.pl.shade_min		  = (int)num("PRGPU_PL_SHADE_MIN", k.pl.shade_min, 1, 64);
@@ -125,7 +127,6 @@ Knobs read_knobs()
 		k.force_features = (uint32_t)strtoul(env, nullptr, 0);
 	k.debug_counters  = getenv("PRGPU_DEBUG_COUNTERS") != nullptr;
 	k.dump_block_life = getenv("PRGPU_DUMP_BLOCK_LIFE");
-	k.trace_ranges	  = (int)num("PRGPU_TRACE_RANGES", -1, -1, 1);
 	return k;
 }
 
@@ -140,17 +141,12 @@ struct TraceRange {
 	static bool bind()
 	{
 		// Only when a profiler is already in the process (rocprofv3 preloads the roctx library: RTLD_NOLOAD finds it without loading
-		// anything), or when PRGPU_TRACE_RANGES=1 asks for it: a production host does not get the roctx / rocprofiler-register stack
-		// pulled into it for a diagnostics feature.  RTLD_LOCAL; a candidate that lacks the two symbols is closed again.
+		// anything): a production host does not get the roctx / rocprofiler-register stack pulled into it for a diagnostics feature.
+		// RTLD_LOCAL; a candidate that lacks the two symbols is closed again.  (The knob that forced the load or switched the ranges off
+		// without a profiler, PRGPU_TRACE_RANGES, went when PRGPU_BVH_LEAF came: nothing in the tree used it.)
 		static const bool bound = [] {
-			const int knob	 = read_knobs().trace_ranges;
-			const bool force = knob == 1;
-			if (knob == 0)
-				return false;
 			for (const char* name : { "librocprofiler-sdk-roctx.so.1", "librocprofiler-sdk-roctx.so", "libroctx64.so.4", "libroctx64.so" }) {
 				void* lib = dlopen(name, RTLD_NOW | RTLD_LOCAL | RTLD_NOLOAD);
-				if (!lib && force)
-					lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
 				if (!lib)
 					continue;
 				push_fn() = reinterpret_cast<PushFn>(dlsym(lib, "roctxRangePushA"));
@@ -192,6 +188,7 @@ struct prgpu_scene {
 	std::vector<void*> allocations;
 	uint32_t bvh_units = 0; // 64-byte units of the BVH record array
 	uint32_t bvh_stack_bound = 0, bvh_top = 0;
+	int bvh_leaf = 3; // the leaf policy of the tree that was built (device/bvh.h): 1 = every triangle a single 64-byte leaf
 	float bvh_cost4 = 0.0f, bvh_cost6 = 0.0f; // the builder's estimates for the 4- and the 6-wide tree (prgpu_pipeline_info)
 	int pp_shader_waves = -1; // persistent kernel: dedicated shading waves per block, decided after the first launch (-1: not yet)
 	double pp_shading_share = 0.0; // ... from this measured share of shading passes in the wave time
@@ -625,6 +622,9 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 		return fail(PRGPU_EINVAL, "PRGPU_BVH_TOP must be auto, file, area or morton");
 	if (s->knobs.bvh_parity == KNOB_INVALID)
 		return fail(PRGPU_EINVAL, "PRGPU_BVH_PARITY must be auto, even or odd");
+	if (s->knobs.bvh_leaf == KNOB_INVALID)
+		return fail(PRGPU_EINVAL, "PRGPU_BVH_LEAF must be auto, 3 or 1");
+	bin.leaf = s->knobs.bvh_leaf;
 	bin.width = s->knobs.bvh_width;
 	bin.top	  = s->knobs.bvh_top;
 	bin.parity = s->knobs.bvh_parity;
@@ -643,6 +643,10 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 	sc.bvh_wide = bout.wide ? 1u : 0u;
 	s->bvh_cost4 = bout.cost4;
 	s->bvh_cost6 = bout.cost6;
+	s->bvh_leaf	 = bout.leaf;
+	if (s->knobs.debug_counters)
+		fprintf(stderr, "[prgpu] BVH leaf policy %d (PRGPU_BVH_LEAF=%s): price %.3f with 128-byte leaves, %.3f with single leaves (0 = not built); the built tree: %.2f inner, %.2f 128-byte-leaf, %.2f single-leaf records expected per ray through the scene's box\n",
+				bout.leaf, s->knobs.bvh_leaf == 0 ? "auto" : (s->knobs.bvh_leaf == 1 ? "1" : "3"), bout.price3, bout.price1, bout.visits[0], bout.visits[1], bout.visits[2]);
 	s->bvh_stack_bound = bout.stack_bound;
 	s->bvh_top = (uint32_t)bout.top;
 	sc.n_leaf  = bout.n_leaf;
@@ -1596,6 +1600,11 @@ int prgpu_trace_counters_get(prgpu_scene* s, prgpu_trace_counters* out)
 	out->leaves_any	   = host[PRGPU_STAT_COUNT + 3];
 	out->node_bytes	   = sizeof(prd::Rec64); // inner record (4-wide, quantised child boxes)
 	out->leaf_bytes	   = 2 * sizeof(prd::Rec64); // leaf record (<= 3 triangles)
+	if (s->bvh_leaf == 1) { // a tree of single leaves: 64-byte leaf records; a 128-byte leaf (an analytic primitive's) counts as two
+		out->leaf_bytes		= sizeof(prd::Rec64);
+		out->leaves_closest = 2 * out->leaves_closest - host[PRGPU_STAT_COUNT + 30];
+		out->leaves_any		= 2 * out->leaves_any - host[PRGPU_STAT_COUNT + 31];
+	}
 	out->ray_bytes	   = 32; // o,tmin + d,tmax
 	out->hit_bytes	   = 16; // t,u,v,tri
 	out->wave_steps_closest = host[PRGPU_STAT_COUNT + 4];
@@ -1702,7 +1711,7 @@ int prgpu_trace_closest(prgpu_scene* s, uint32_t n, const float* org, const floa
 	// PRGPU_TRACE_SPLIT=0 or the tree has too many records for the 24-bit task field
 	const bool split = read_knobs().trace_split;
 	if (split && s->sc.n_leaf > 0 && s->bvh_units < (1u << 24) && !(s->sc.features & (prd::FEAT_SPHERES | prd::FEAT_QUADRICS | prd::FEAT_DISKS))) {
-		prd::launch_service_closest_split(s->sc, n, d_org, d_dir, d_tmin, d_tmax, d_e, d_p, d_u, d_v, d_t, s->ws, const_cast<uint32_t*>(s->sc.tri_slot), s->gstats, s->stream);
+		prd::launch_service_closest_split(s->sc, n, d_org, d_dir, d_tmin, d_tmax, d_e, d_p, d_u, d_v, d_t, s->ws, const_cast<uint32_t*>(s->sc.tri_slot), s->gstats, s->bvh_leaf == 1, s->stream);
 	} else
 		prd::launch_service_closest(s->sc, n, d_org, d_dir, d_tmin, d_tmax, d_e, d_p, d_u, d_v, d_t, s->ws, s->gstats, s->stream);
 	s->time_end(s->stream);
