@@ -52,7 +52,8 @@ extern "C" {
                                prgpu_pipeline_info_get, prgpu_comm_query, prgpu_reduced_planes; PRGPU_ENTITY_DISK and PRGPU_SPEC_IMAGE are new enumerators, no field moved;
                                prgpu_image_load came with the latter; PRGPU_MAT_OREN_NAYAR, PRGPU_MAT_NULL, PRGPU_MAT_BLEND and PRGPU_MAT_ADD are new
                                enumerators that reuse fields of prgpu_material, no field moved; PRGPU_SPEC_ADD .. PRGPU_SPEC_PEAK are new enumerators
-                               that reuse lhs / rhs / p of prgpu_spectrum, no field moved */
+                               that reuse lhs / rhs / p of prgpu_spectrum, no field moved; a BLEND / ADD may name a BLEND / ADD as a child
+                               (PRGPU_MIX_MAX_DEPTH, PRGPU_MIX_MAX_LEAVES) and prgpu_mix_leaves reports the flattened tree, no field moved */
 #define PRGPU_INVALID_ID 0xFFFFFFFFu /* PR_INVALID_ID, src/base/config/Constants.inl:6 */
 
 enum {
@@ -147,13 +148,20 @@ enum { PRGPU_MAT_LAMBERT = 0, PRGPU_MAT_DIELECTRIC = 1, PRGPU_MAT_CONDUCTOR = 2,
  *             sigma^2 = roughness^2, s = V.L - NdotL NdotV, t = 1 when s < eps else max(NdotL, NdotV); `albedo` and `roughness_x`; one sided: no light
  *             from below the normal (max(0, NdotL)), its samples are NOT flipped to the viewer's side, and there is no `two_sided`
  * NULL        null.cpp: delta-only, passes the ray on unchanged (L = -V, weight 1, pdf 1, specular transmission); draws nothing
- * BLEND       blend.cpp (`blend`, `mix`): two EARLIER materials of the array, neither a BLEND / ADD itself, and a factor f clamped to [0, 1] at
- *             evaluation: eval (1 - f) w1 + f w2 (weight and pdf alike; a delta-only child drops out and the other keeps its factor), sample: one
+ * BLEND       blend.cpp (`blend`, `mix`): two EARLIER materials of the array (plain ones or BLEND / ADD: the trees nest, within the two bounds
+ *             below) and a factor f clamped to [0, 1] at evaluation: eval (1 - f) w1 + f w2 (weight and pdf alike; a delta-only child drops out and the other keeps its factor), sample: one
  *             number picks child 1 when it is < 1 - f, and the child's integral weight AND pdf are scaled by its selection probability
  * ADD         add.cpp: the same structure: eval w1 + w2 with the mean of the pdfs (one delta-only child: the other's weight, half its pdf),
  *             sample: one number against 0.5 picks the child, whose pdf is halved and whose weight is kept
- * A BLEND / ADD whose two children are delta-only is delta-only itself. */
+ * A BLEND / ADD whose two children are delta-only is delta-only itself, recursively.  A child that is a BLEND / ADD is evaluated and sampled by
+ * the same rules (the reference recurses, blend.cpp, add.cpp): scene creation flattens the tree below every BLEND / ADD into a table of the
+ * plain leaves its eval reaches, each with the product of the factors on its path (prgpu_mix_leaves below). */
 enum { PRGPU_MAT_OREN_NAYAR = 7, PRGPU_MAT_NULL = 8, PRGPU_MAT_BLEND = 9, PRGPU_MAT_ADD = 10 };
+/* Bounds of a BLEND / ADD tree; a description beyond either is refused with PRGPU_EUNSUPPORTED and the constant's name.  Both are choices, not
+ * measurements: eight leaves bound a vertex's next event estimation at eight closure evaluations and keep a table row small (28 words);
+ * depth 4 holds a chain of five layers and a balanced tree of eight leaves. */
+#define PRGPU_MIX_MAX_DEPTH  4 /* BLEND / ADD materials on any path from a root to a leaf */
+#define PRGPU_MIX_MAX_LEAVES 8 /* plain materials below one root, a shared child counted once per path to it */
 enum { PRGPU_MATF_ANISOTROPIC = 1u,      /* roughness_y given as its own parameter (the reference compares the NODES, not the values) */
        PRGPU_MATF_NO_VNDF = 2u,          /* `:vndf false`: sample the plain GGX normal distribution (Microfacet.h:225-256; the anisotropic form
                                             through the backend's shared fp32 tan / atan) */
@@ -166,10 +174,11 @@ typedef struct prgpu_material {
 	uint32_t kind;
 	uint32_t albedo;       /* spectrum index.  LAMBERT, OREN_NAYAR: `albedo`; every other kind: `specularity` (reflection tint, default 1);
 	                          NULL, BLEND, ADD: any valid index (not read) */
-	uint32_t two_sided;    /* LAMBERT `two_sided`, default true (lambert.cpp:108); BLEND, ADD: material index of `material1` (smaller than the combinator's own) */
+	uint32_t two_sided;    /* LAMBERT `two_sided`, default true (lambert.cpp:108); BLEND, ADD: material index of `material1`: any kind, BLEND / ADD included, with an index
+	                          smaller than the combinator's own (which keeps the graph acyclic) */
 	uint32_t ior;          /* (ROUGH_)DIELECTRIC: `index`/`eta`/`ior` spectrum (default 1.55); (ROUGH_)CONDUCTOR: `eta` (default 1.2) */
 	uint32_t transmission; /* (ROUGH_)DIELECTRIC: `transmission` tint spectrum, or PRGPU_INVALID_ID = same as specularity (dielectric.cpp:92-96) */
-	uint32_t thin;         /* DIELECTRIC: `thin` sheet approximation (dielectric.cpp:69-72,98-101); PRINCIPLED: `thin`; BLEND, ADD: material index of `material2` */
+	uint32_t thin;         /* DIELECTRIC: `thin` sheet approximation (dielectric.cpp:69-72,98-101); PRINCIPLED: `thin`; BLEND, ADD: material index of `material2` (as `material1`) */
 	uint32_t k;            /* (ROUGH_)CONDUCTOR: `k`/`kappa` absorption index spectrum (default 2.605) */
 	uint32_t flags;        /* PRGPU_MATF_* (rough kinds) */
 	float roughness_x;     /* rough kinds: `roughness_x` or `roughness` (constant scalar; textures are out of scope); OREN_NAYAR: `roughness` (default 0.5);
@@ -413,6 +422,23 @@ int  prgpu_write_rgb_coeff_table(const char* path, uint32_t resolution, int thre
  * PRGPU_EINVAL, as is a damaged file (checksum, stream, filter); a missing or truncated one PRGPU_EIO.  channels_in_file and linearised
  * may be NULL.  Host only. */
 int  prgpu_image_load(const char* path, uint32_t* width, uint32_t* height, uint32_t* channels_in_file, int* linearised, float* rgb);
+/* The tree below material `material` as the device reads it (one table row per BLEND / ADD, compiled at scene creation): the plain leaves
+ * IMaterial::eval reaches, depth first, child 1 before child 2, each with the coefficient of its weight and of its pdf -- eval of the root is
+ * sum weight_i w_i and sum pdf_i p_i.  The coefficients are fp32 products formed from the root down: blend, neither child delta-only: (1 - f)
+ * resp. f on both; add: 1 on the weight, 0.5 on the pdf; with ONE delta-only child (recursively) only the other one is reached, with the same
+ * factors; with two, nothing is.  *delta_only: hasOnlyDeltaDistribution of the root (no leaf reached).  *symbol_leaf: index into `out` of the
+ * leaf whose scattering type the root reports (blend, neither delta-only: child 1 when f <= 0.5; add: child 1; else the child that is not
+ * delta-only), PRGPU_INVALID_ID without a leaf.  *flag_leaf: the leaf whose delta flag eval reports -- the single leaf at the end of a chain
+ * of one-sided forms -- or PRGPU_INVALID_ID where a two-children form is on the way (it sets none).  A plain material gives one leaf with
+ * 1, 1 and symbol_leaf = flag_leaf = 0.  `out` holds PRGPU_MIX_MAX_LEAVES entries, or is NULL to query the rest; the other pointers may be
+ * NULL.  Checks the tree only (indices, the smaller-index rule, the two bounds, a finite factor), with the messages of prgpu_scene_create.
+ * Host only: needs no device. */
+typedef struct prgpu_mix_leaf {
+	uint32_t material; /* a plain material (not BLEND / ADD) */
+	float weight;      /* a_i */
+	float pdf;         /* b_i */
+} prgpu_mix_leaf;
+int  prgpu_mix_leaves(const prgpu_scene_desc* desc, uint32_t material, prgpu_mix_leaf* out, uint32_t* n, uint32_t* delta_only, uint32_t* symbol_leaf, uint32_t* flag_leaf);
 
 /* -- scene -------------------------------------------------------------------------------- */
 /* Validates + uploads the scene to HIP device `device`, builds the two-level LBVH on the device,

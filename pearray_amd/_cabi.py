@@ -23,6 +23,7 @@ SPEC_OPS = {"smul": SPEC_MUL, "sadd": SPEC_ADD, "ssub": SPEC_SUB, "sdiv": SPEC_D
 EXPR_MAX_STACK, EXPR_MAX_PROGRAM = 4, 64
 MAT_LAMBERT, MAT_DIELECTRIC, MAT_CONDUCTOR, MAT_ROUGH_CONDUCTOR, MAT_ROUGH_DIELECTRIC, MAT_PRINCIPLED, MAT_MIRROR = 0, 1, 2, 3, 4, 5, 6
 MAT_OREN_NAYAR, MAT_NULL, MAT_BLEND, MAT_ADD = 7, 8, 9, 10   # BLEND / ADD: two_sided, thin = the two children's material indices, roughness_x = the blend factor
+MIX_MAX_DEPTH, MIX_MAX_LEAVES = 4, 8                         # PRGPU_MIX_MAX_DEPTH, PRGPU_MIX_MAX_LEAVES: the bounds of a BLEND / ADD tree
 MATF_ANISOTROPIC, MATF_NO_VNDF, MATF_HAS_TRANSMISSION = 1, 2, 4
 PRINCIPLED_PARAMS = ("diffuse_transmission", "specular_transmission", "specular_tint", "anisotropic", "flatness", "metallic", "sheen",
                      "sheen_tint", "clearcoat", "clearcoat_gloss")
@@ -62,6 +63,10 @@ class Material(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("albedo", C.c_uint32), ("two_sided", C.c_uint32), ("ior", C.c_uint32),
                 ("transmission", C.c_uint32), ("thin", C.c_uint32), ("k", C.c_uint32), ("flags", C.c_uint32),
                 ("roughness_x", C.c_float), ("roughness_y", C.c_float), ("principled", C.c_float * 10)]
+
+
+class MixLeaf(C.Structure):  # prgpu_mix_leaf
+    _fields_ = [("material", C.c_uint32), ("weight", C.c_float), ("pdf", C.c_float)]
 
 
 class Emission(C.Structure):
@@ -181,6 +186,7 @@ SYMBOLS = {
     "prgpu_rgb_to_coeffs": (C.c_int, [_F32P, _F32P]),
     "prgpu_write_rgb_coeff_table": (C.c_int, [C.c_char_p, C.c_uint32, C.c_int]),
     "prgpu_image_load": (C.c_int, [C.c_char_p, _U32P, _U32P, _U32P, C.POINTER(C.c_int), _F32P]),
+    "prgpu_mix_leaves": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, _U32P, _U32P, _U32P, _U32P]),
     "prgpu_scene_create": (C.c_int, [C.POINTER(SceneDesc), C.c_int, C.POINTER(_VP)]),
     "prgpu_scene_destroy": (None, [_VP]),
     "prgpu_set_tiles": (C.c_int, [_VP, C.POINTER(Tile), C.c_uint32]),

@@ -313,6 +313,21 @@ def rccl_available():
     return abi.load().prgpu_comm_unique_id(buf) == 0
 
 
+def mix_leaves(desc, material):
+    """The tree below `material` as the device reads it (prgpu_mix_leaves; needs no device): {"leaves": [(material, weight coefficient,
+    pdf coefficient), ...] in evaluation order, "delta_only": bool, "symbol_leaf": index into leaves or None, "flag_leaf": likewise}.
+    `desc`: a scene description, or a scene object that holds one (`.desc`).  A plain material gives one leaf with (1, 1)."""
+    d = getattr(desc, "desc", desc)
+    out = (abi.MixLeaf * abi.MIX_MAX_LEAVES)()
+    n, delta, sym, flag = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    abi.check(abi.load().prgpu_mix_leaves(C.byref(d), int(material), out, C.byref(n), C.byref(delta), C.byref(sym), C.byref(flag)))
+
+    def index(v):
+        return None if v.value == abi.INVALID_ID else int(v.value)
+    return {"leaves": [(int(l.material), np.float32(l.weight), np.float32(l.pdf)) for l in out[:n.value]], "delta_only": bool(delta.value),
+            "symbol_leaf": index(sym), "flag_leaf": index(flag)}
+
+
 def write_exr(path, channels):
     """channels: dict name -> float32 array [H, W]; written by the library's EXR writer (uncompressed scanline, float)."""
     lib = abi.load()

@@ -1579,7 +1579,11 @@ __device__ __forceinline__ void material_eval(const DevScene& s, const prgpu_mat
 	pdf				= blob(dt * PR_INV_PI_F);
 }
 // ---- BlendMaterial / AddMaterial (blend.cpp, add.cpp): the FEAT_MIX_MATERIALS builds only.  A combinator's record names its two children
-// (two_sided = material1, thin = material2: plain materials with a smaller index) and, for BLEND, the factor (roughness_x).
+// (two_sided = material1, thin = material2: materials with a smaller index, plain ones or combinators) and, for BLEND, the factor
+// (roughness_x).  The tree below it was flattened at scene creation (host/mix_tree.h): one row in DevScene::tables, behind the spectral
+// tables and the expression programs, of count, the root's delta-only bit, symbol leaf, flag leaf, then count x (leaf material, a, b).
+// The albedo node copy of its DevMaterial, which nothing reads, carries the row's offset (table_offset) and the delta-only bit (table_count).
+constexpr uint32_t MIX_ROW_SYMBOL = 2, MIX_ROW_FLAG = 3, MIX_ROW_HEADER = 4, MIX_ROW_LEAF = 3;
 // IMaterial::hasOnlyDeltaDistribution of a plain kind
 __device__ __forceinline__ bool mix_delta_only(uint32_t kind) { return kind == PRGPU_MAT_DIELECTRIC || kind == PRGPU_MAT_CONDUCTOR || kind == PRGPU_MAT_MIRROR || kind == PRGPU_MAT_NULL; }
 // a child as the vertex would have loaded it had the triangle named it: textures resolved at `uv`, albedo at the path's wavelengths
@@ -1598,32 +1602,33 @@ __device__ __forceinline__ void mix_child(const DevScene& sc, uint32_t id, const
 	albedo = rough ? blob(0) : albedo_eval<(FEATS & FEAT_IMAGES) != 0u, (FEATS & FEAT_EXPR) != 0u>(sc, m, dm.albedo, dm.m.albedo, wl, uv);
 }
 // IMaterial::eval of the vertex's material for next event estimation in the FEAT_MIX_MATERIALS builds (the others call material_eval, as
-// before).  Without a combinator this is material_eval.  With one
-// (BlendMaterial::eval, blend.cpp:41-75; AddMaterial::eval, add.cpp:40-66) the children that are not delta-only are evaluated, ONE call
-// site in a loop, and combined: (1 - f) w1 + f w2 for weight and pdf, resp. w1 + w2 with the pdfs' mean; with one delta-only child the other
-// one alone, scaled by its factor resp. with half its pdf, and with ITS delta flag (the two-children forms never set one).  sym_kind /
-// sym_roughness: kind and roughness_x of the material whose scattering type the pair reports (blend: child 1 when f <= 0.5; add: child 1).
+// before).  Without a combinator this is material_eval.  With one (BlendMaterial::eval, blend.cpp:41-75; AddMaterial::eval, add.cpp:40-66,
+// which recurse) it is linear in the plain leaves the tree's forms reach: weight = sum a_i w_i, pdf = sum b_i p_i over the leaves of the
+// combinator's row (at `row` in DevScene::tables), ONE call site in a loop.  The coefficients are the host's products of (1 - f) / f resp.
+// 1 / 0.5 from the root down, so a row of two leaves is the two-children arithmetic it replaces, bit for bit.  The delta flag is the flag
+// leaf's (the end of a chain of one-sided forms; a two-children form sets none), sym_kind / sym_roughness are kind and roughness_x of the
+// symbol leaf, the material whose scattering type the root reports (blend: child 1 when f <= 0.5; add: child 1; per level).
 template <uint32_t FEATS>
-__device__ __forceinline__ void vertex_eval(const DevScene& sc, const prgpu_material& mat, const Blob& albedo, bool comb, bool delta1, bool delta2, const Blob& wl, const Blob& cie_y, V3 Vt,
-											V3 Lt, Blob& weight, Blob& pdf, bool& delta, uint32_t& sym_kind, float& sym_roughness, const float* uv)
+__device__ __forceinline__ void vertex_eval(const DevScene& sc, const prgpu_material& mat, const Blob& albedo, bool comb, uint32_t row, const Blob& wl, const Blob& cie_y, V3 Vt, V3 Lt,
+											Blob& weight, Blob& pdf, bool& delta, uint32_t& sym_kind, float& sym_roughness, const float* uv)
 {
-	const bool add	 = mat.kind == PRGPU_MAT_ADD;
-	const float f	 = fminf(1.0f, fmaxf(0.0f, mat.roughness_x));
-	const bool both	 = comb && !delta1 && !delta2;
-	const int sym_of = !comb ? 0 : (both ? ((add || f <= 0.5f) ? 0 : 1) : (delta1 ? 1 : 0));
-	weight			 = blob(0);
-	pdf				 = blob(0);
-	delta			 = false;
-	const int n		 = comb ? 2 : 1;
+	const uint32_t* r  = reinterpret_cast<const uint32_t*>(sc.tables) + row; // (read when comb)
+	const uint32_t n   = comb ? r[0] : 1u;
+	const uint32_t sym = comb ? r[MIX_ROW_SYMBOL] : 0u, flg = comb ? r[MIX_ROW_FLAG] : 0u;
+	weight			   = blob(0);
+	pdf				   = blob(0);
+	delta			   = false;
 #pragma unroll 1
-	for (int c = 0; c < n; ++c) {
-		if (comb && (c ? delta2 : delta1))
-			continue;
+	for (uint32_t c = 0; c < n; ++c) {
 		prgpu_material cm;
 		Blob ca;
+		float a = 1.0f, b = 1.0f;
 		if (comb) {
+			const uint32_t* l = r + MIX_ROW_HEADER + MIX_ROW_LEAF * c;
 			bool rough;
-			mix_child<FEATS>(sc, c ? mat.thin : mat.two_sided, wl, uv, cm, ca, rough);
+			mix_child<FEATS>(sc, l[0], wl, uv, cm, ca, rough);
+			a = __uint_as_float(l[1]);
+			b = __uint_as_float(l[2]);
 		} else {
 			cm = mat;
 			ca = albedo;
@@ -1631,26 +1636,22 @@ __device__ __forceinline__ void vertex_eval(const DevScene& sc, const prgpu_mate
 		Blob w, p;
 		bool d;
 		material_eval<FEATS>(sc, cm, ca, wl, cie_y, Vt, Lt, w, p, d, uv);
-		const float sw = (!comb || add) ? 1.0f : (c ? f : 1 - f);
-		const float sp = !comb ? 1.0f : (add ? (both ? 1.0f : 0.5f) : sw);
 		if (!comb) {
 			weight = w;
 			pdf	   = p;
 		} else {
 			for (int i = 0; i < 4; ++i) {
-				weight.v[i] += w.v[i] * sw;
-				pdf.v[i] += p.v[i] * sp;
+				weight.v[i] += w.v[i] * a;
+				pdf.v[i] += p.v[i] * b;
 			}
 		}
-		if (!both)
+		if (c == flg)
 			delta = d;
-		if (c == sym_of) {
+		if (c == sym) {
 			sym_kind	  = cm.kind;
 			sym_roughness = cm.roughness_x;
 		}
 	}
-	if (both && add)
-		pdf = pdf / 2.0f;
 }
 
 // CIESimpleSkyLight::radiance (cie_sky.cpp:108-126) for a world direction; (z + 1.01)^10 by squaring in fp32
@@ -2021,15 +2022,16 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 			uint64_t rnd			 = ps.rng[pixel];
 			const bool deltaMat		 = (FEATS & FEAT_DELTA_MATERIALS) && (mat.kind == PRGPU_MAT_DIELECTRIC || mat.kind == PRGPU_MAT_CONDUCTOR || mat.kind == PRGPU_MAT_MIRROR); // IMaterial::hasOnlyDeltaDistribution
 			const bool roughMat		 = (FEATS & FEAT_ROUGH_MATERIALS) && (mat.kind == PRGPU_MAT_ROUGH_CONDUCTOR || mat.kind == PRGPU_MAT_ROUGH_DIELECTRIC || mat.kind == PRGPU_MAT_PRINCIPLED);
-			// what guards next event estimation and the Russian roulette draw: a blend / add is delta-only when both children are
-			// (blend.cpp:156-173, add.cpp:141-158).  (These stay constants of the kernels without FEAT_MIX_MATERIALS: their code does not change.)
-			const bool delta1 = comb && mix_delta_only(sc.materials[mat.two_sided].m.kind), delta2 = comb && mix_delta_only(sc.materials[mat.thin].m.kind);
-			const bool deltaOnly = comb ? (delta1 && delta2) : (deltaMat || (MIX && mat.kind == PRGPU_MAT_NULL));
+			// what guards next event estimation and the Russian roulette draw: a blend / add is delta-only when both children are, recursively
+			// (blend.cpp:156-173, add.cpp:141-158): the root's bit, worked out when its tree was flattened.  (These stay constants of the kernels
+			// without FEAT_MIX_MATERIALS: their code does not change.)
+			const uint32_t mix_row = comb ? dmat.albedo.table_offset : 0u;
+			const bool deltaOnly   = comb ? dmat.albedo.table_count != 0u : (deltaMat || (MIX && mat.kind == PRGPU_MAT_NULL));
 			const Blob cie_y_blob	 = blob4(cie.y[0], cie.y[1], cie.y[2], cie.y[3]);
 			// albedo / specularity at the path's wavelengths, once: IMaterial::eval and ::sample of a vertex evaluate the same node at
 			// the same wavelengths (lambert.cpp:38,66; mirror / conductor / dielectric sample).  The rough closures fetch their own.
 			constexpr bool IMG	= (FEATS & FEAT_IMAGES) != 0u; // material parameters may be image textures: their evaluation takes the point's uv
-			Blob albedo_v		= roughMat ? blob(0) : albedo_eval<IMG, EXPR>(sc, mat, dmat.albedo, dmat.m.albedo, wl, gp.uv);
+			Blob albedo_v		= (roughMat || comb) ? blob(0) : albedo_eval<IMG, EXPR>(sc, mat, dmat.albedo, dmat.m.albedo, wl, gp.uv); // (a blend / add: its leaves fetch their own; its node copy holds the row)
 			if (cfg.nee && !deltaOnly && !hasEmission && (sc.n_lights + ((FEATS & FEAT_INFINITE_LIGHTS) ? sc.n_inf_lights : 0u))) { // direct.cpp:100-101
 				// ---- handleNEE
 				do {
@@ -2065,7 +2067,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 						uint32_t sym_kind	= 0u; // (FEAT_MIX_MATERIALS) the material whose scattering type the connection reports: a blend / add names one of its children
 						float sym_roughness = 0.0f;
 						if constexpr (MIX)
-							vertex_eval<FEATS>(sc, mat, albedo_v, comb, delta1, delta2, wl, cie_y_blob, Vt, Lt, weight, bsdf_pdf, evalDelta, sym_kind, sym_roughness, gp.uv);
+							vertex_eval<FEATS>(sc, mat, albedo_v, comb, mix_row, wl, cie_y_blob, Vt, Lt, weight, bsdf_pdf, evalDelta, sym_kind, sym_roughness, gp.uv);
 						else
 							material_eval<FEATS>(sc, mat, albedo_v, wl, cie_y_blob, Vt, Lt, weight, bsdf_pdf, evalDelta, gp.uv);
 						if (evalDelta) // direct.cpp:269-270
@@ -2180,7 +2182,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 					uint32_t sym_kind	= 0u; // (FEAT_MIX_MATERIALS) the material whose scattering type the connection reports: a blend / add names one of its children
 					float sym_roughness = 0.0f;
 					if constexpr (MIX)
-						vertex_eval<FEATS>(sc, mat, albedo_v, comb, delta1, delta2, wl, cie_y_blob, Vt, Lt, weight, bsdf_pdf, evalDelta, sym_kind, sym_roughness, gp.uv);
+						vertex_eval<FEATS>(sc, mat, albedo_v, comb, mix_row, wl, cie_y_blob, Vt, Lt, weight, bsdf_pdf, evalDelta, sym_kind, sym_roughness, gp.uv);
 					else
 						material_eval<FEATS>(sc, mat, albedo_v, wl, cie_y_blob, Vt, Lt, weight, bsdf_pdf, evalDelta, gp.uv);
 					if (evalDelta) // direct.cpp:269-270
@@ -2245,15 +2247,29 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 				float mix_weight = 1.0f, mix_pdf = 1.0f;
 				bool child_rough = false;
 				if (comb) {
-					// BlendMaterial::sample (blend.cpp:104-122), AddMaterial::sample (add.cpp:92-110): ONE number picks the child, which then
-					// samples as if the vertex had hit it; blend scales its integral weight AND its pdf by the selection probability
-					// (the weight is not divided by it), add halves the pdf only
-					const bool add	  = mat.kind == PRGPU_MAT_ADD;
-					const float f	  = fminf(1.0f, fmaxf(0.0f, mat.roughness_x));
-					const bool second = !(rng_float(rnd) < (add ? 0.5f : 1 - f));
-					mix_pdf			  = add ? 0.5f : (second ? f : 1 - f);
-					mix_weight		  = add ? 1.0f : mix_pdf;
-					const uint32_t id = second ? mat.thin : mat.two_sided;
+					// BlendMaterial::sample (blend.cpp:104-122), AddMaterial::sample (add.cpp:92-110), which recurse: at every combinator from
+					// the root down ONE number picks the child; the leaf then samples as if the vertex had hit it.  A blend level scales the
+					// integral weight AND the pdf by its selection probability (the weight is not divided by it), an add level halves the pdf
+					// only; the factors compound.  A round reads kind, children and factor of the current record; the leaf is loaded once.
+					uint32_t kind = mat.kind, c1 = mat.two_sided, c2 = mat.thin, id = c1;
+					float factor  = mat.roughness_x;
+#pragma unroll 1
+					for (int level = 0;; ++level) {
+						const bool add	  = kind == PRGPU_MAT_ADD;
+						const float f	  = fminf(1.0f, fmaxf(0.0f, factor));
+						const bool second = !(rng_float(rnd) < (add ? 0.5f : 1 - f));
+						const float sel	  = add ? 0.5f : (second ? f : 1 - f);
+						mix_pdf			  = mix_pdf * sel;
+						mix_weight		  = add ? mix_weight : mix_weight * sel;
+						id				  = second ? c2 : c1;
+						const prgpu_material& next = sc.materials[id].m;
+						kind					   = next.kind;
+						if (!(kind == PRGPU_MAT_BLEND || kind == PRGPU_MAT_ADD) || level + 1 >= PRGPU_MIX_MAX_DEPTH) // (the bound: validated at scene creation)
+							break;
+						c1	   = next.two_sided;
+						c2	   = next.thin;
+						factor = next.roughness_x;
+					}
 					mix_child<FEATS>(sc, id, wl, gp.uv, mat, albedo_v, child_rough);
 				}
 				// the material that samples: the vertex's own, or the child just chosen (now in `mat`)

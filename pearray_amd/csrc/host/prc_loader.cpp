@@ -34,6 +34,7 @@
 
 #include "datalisp.h"
 #include "image_reader.h"
+#include "mix_tree.h"
 #include "setup.h"
 #include "spectral_expr.h"
 
@@ -84,6 +85,7 @@ struct Loader {
 	prgpu_prc_options opt;
 	prgpu_settings settings;
 	std::map<std::string, uint32_t> material_ids, emission_ids;
+	std::vector<prgpu_host::MixExtent> material_extent; // per material: the size of the blend / add tree below it (a plain one: depth 0, one leaf)
 	std::map<std::string, Mesh> meshes;
 	std::map<std::string, prgpu_camera> cameras;
 	std::string first_camera, selected_camera;
@@ -1365,13 +1367,18 @@ struct Loader {
 				const auto it		  = material_ids.find(ref);
 				if (it == material_ids.end())
 					fail(PRGPU_EINVAL, where(g) + ": material '" + name + "' refers to unknown material '" + ref + "' (:" + key + " names a material declared earlier)");
-				const uint32_t kind = out.materials[it->second].kind;
-				if (kind == PRGPU_MAT_BLEND || kind == PRGPU_MAT_ADD)
-					fail(PRGPU_EUNSUPPORTED, where(g) + ": material '" + name + "': a blend or add material ('" + ref + "') as :" + key + " is not supported");
-				return it->second;
+				return it->second; // (a blend or add too: the trees nest, blend.cpp, add.cpp)
 			};
 			m.two_sided = child("material1");
 			m.thin		= child("material2");
+			{ // the two bounds of a tree (include/prgpu.h), from the children's extents
+				material_extent.resize(out.materials.size() + 1);
+				const prgpu_host::MixExtent e = prgpu_host::mix_extent_of(material_extent[m.two_sided], material_extent[m.thin]);
+				const std::string why		  = prgpu_host::mix_extent_refusal(e, where(g) + ": material '" + name + "'");
+				if (!why.empty())
+					fail(PRGPU_EUNSUPPORTED, why);
+				material_extent[out.materials.size()] = e;
+			}
 			if (m.kind == PRGPU_MAT_BLEND) {
 				if (const Value* v = g.get("factor")) {
 					if (!v->is_number())

@@ -12,6 +12,7 @@
 //   filter taps                       filter/FilterCache.h:8-25 + plugins/main/filter/*.cpp
 //   Russian-roulette table            vcm/vcm/RussianRoulette.h:22-35
 #include "setup.h"
+#include "mix_tree.h"
 #include "spectral_expr.h"
 
 #include <algorithm>
@@ -1005,6 +1006,25 @@ void filter_taps(const prgpu_scene_desc* d, HostTables& t)
 	t.single_tap	= (live == 1 && t.centre_weight > EPS_F) ? 1u : 0u;
 }
 
+// A BLEND / ADD material `i` whose predecessors passed: two_sided / thin name the children, roughness_x is the blend factor (include/prgpu.h).
+// Fills extent[i] from the children's.
+int check_combinator(const prgpu_material* mats, uint32_t i, std::vector<MixExtent>& extent, std::string& err)
+{
+	const prgpu_material& m = mats[i];
+	const std::string what	= std::string(m.kind == PRGPU_MAT_BLEND ? "blend" : "add") + " material " + std::to_string(i);
+	for (uint32_t child : { m.two_sided, m.thin })
+		if (child >= i) { // (a forward reference, or the material itself: children with a smaller index keep the graph acyclic)
+			err = what + ": a child must be a material with a smaller index";
+			return PRGPU_EUNSUPPORTED;
+		}
+	if (m.kind == PRGPU_MAT_BLEND && !std::isfinite(m.roughness_x)) {
+		err = what + ": the factor must be finite";
+		return PRGPU_EINVAL;
+	}
+	extent[i] = mix_extent_of(extent[m.two_sided], extent[m.thin]);
+	err		  = mix_extent_refusal(extent[i], what);
+	return err.empty() ? PRGPU_OK : PRGPU_EUNSUPPORTED;
+}
 } // namespace
 
 int validate_desc(const prgpu_scene_desc* d, std::string& err)
@@ -1164,20 +1184,15 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 		if (expr_info[i].expression && expr_info[i].length > PRGPU_EXPR_MAX_PROGRAM)
 			return bad(("spectral expression node " + std::to_string(i) + ": its program is longer than PRGPU_EXPR_MAX_PROGRAM (" + std::to_string(PRGPU_EXPR_MAX_PROGRAM) + " words)").c_str(), PRGPU_EUNSUPPORTED);
 	}
+	std::vector<MixExtent> mix_extent(d->n_materials);
 	for (uint32_t i = 0; i < d->n_materials; ++i) {
 		const prgpu_material& m = d->materials[i];
 		if (m.kind > PRGPU_MAT_ADD)
 			return bad("unknown material kind", PRGPU_EUNSUPPORTED);
-		if (m.kind == PRGPU_MAT_BLEND || m.kind == PRGPU_MAT_ADD) { // two_sided / thin: the children, roughness_x: the blend factor (include/prgpu.h)
-			const char* what = m.kind == PRGPU_MAT_BLEND ? "blend" : "add";
-			for (uint32_t child : { m.two_sided, m.thin }) {
-				if (child >= i) // (a forward reference, or the material itself: the children are evaluated as they stand, in one pass)
-					return bad((std::string(what) + " material " + std::to_string(i) + ": a child must be a material with a smaller index").c_str(), PRGPU_EUNSUPPORTED);
-				if (d->materials[child].kind == PRGPU_MAT_BLEND || d->materials[child].kind == PRGPU_MAT_ADD)
-					return bad((std::string(what) + " material " + std::to_string(i) + ": a blend or add material as a child is not supported").c_str(), PRGPU_EUNSUPPORTED);
-			}
-			if (m.kind == PRGPU_MAT_BLEND && !std::isfinite(m.roughness_x))
-				return bad(("blend material " + std::to_string(i) + ": the factor must be finite").c_str());
+		if (mat_is_combinator(m.kind)) {
+			const int rc = check_combinator(d->materials, i, mix_extent, err);
+			if (rc != PRGPU_OK)
+				return rc;
 		}
 		if (m.kind == PRGPU_MAT_OREN_NAYAR && !std::isfinite(m.roughness_x))
 			return bad("oren-nayar roughness must be finite");
@@ -1218,10 +1233,8 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 				return bad("entity wants texture coordinates but none given");
 			if (E.kind != PRGPU_ENTITY_SPHERE || d->tri_material[E.first_tri] == PRGPU_INVALID_ID)
 				continue;
-			const prgpu_material& m = d->materials[d->tri_material[E.first_tri]];
-			auto textured_material	= [&](const prgpu_material& mm) { return textured(mm.albedo) || textured(mm.ior) || textured(mm.k) || textured(mm.transmission); };
-			const bool combinator	= m.kind == PRGPU_MAT_BLEND || m.kind == PRGPU_MAT_ADD; // its children are what the vertex evaluates
-			if (combinator ? (textured_material(d->materials[m.two_sided]) || textured_material(d->materials[m.thin])) : textured_material(m))
+			auto textured_material =[&](const prgpu_material& mm) { return textured(mm.albedo) || textured(mm.ior) || textured(mm.k) || textured(mm.transmission); };
+			if (mix_any_leaf(d->materials, d->tri_material[E.first_tri], textured_material)) // (a blend / add: its leaves are what the vertex evaluates)
 				return bad("textured materials on sphere entities are not supported (their uv needs atan2 / acos)", PRGPU_EUNSUPPORTED);
 		}
 	}
@@ -1449,3 +1462,33 @@ void owned_pixels_morton(uint32_t W, uint32_t H, const prgpu_tile* tiles, uint32
 }
 
 } // namespace prgpu_host
+
+extern "C" int prgpu_mix_leaves(const prgpu_scene_desc* d, uint32_t material, prgpu_mix_leaf* out, uint32_t* n, uint32_t* delta_only, uint32_t* symbol_leaf, uint32_t* flag_leaf)
+{
+	using namespace prgpu_host;
+	if (!d || !d->materials || material >= d->n_materials)
+		return set_last_error(PRGPU_EINVAL, "prgpu_mix_leaves: null description or material index out of range");
+	std::vector<MixExtent> extent(size_t(material) + 1);
+	std::string err;
+	for (uint32_t i = 0; i <= material; ++i) {
+		if (d->materials[i].kind > PRGPU_MAT_ADD)
+			return set_last_error(PRGPU_EUNSUPPORTED, "unknown material kind");
+		if (mat_is_combinator(d->materials[i].kind)) {
+			const int rc = check_combinator(d->materials, i, extent, err);
+			if (rc != PRGPU_OK)
+				return set_last_error(rc, err);
+		}
+	}
+	const MixRow row = mix_flatten(d->materials, material);
+	if (out)
+		std::copy(row.leaves.begin(), row.leaves.end(), out);
+	if (n)
+		*n = (uint32_t)row.leaves.size();
+	if (delta_only)
+		*delta_only = row.delta_only ? 1u : 0u;
+	if (symbol_leaf)
+		*symbol_leaf = row.symbol_leaf;
+	if (flag_leaf)
+		*flag_leaf = row.flag_leaf;
+	return PRGPU_OK;
+}

@@ -18,6 +18,7 @@
 #include "../../include/prgpu.h"
 #include "device/bvh.h"
 #include "device/render.h"
+#include "host/mix_tree.h"
 #include "host/setup.h"
 #include "tables/pr_vf_colors.inl"
 static_assert(sizeof(PR_VF_COLOR_RGB) / sizeof(PR_VF_COLOR_RGB[0]) == prd::VF_COLOURS, "one row per colour index of device/render.h");
@@ -425,13 +426,8 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 		for (uint32_t i = 0; i < d->n_triangles; ++i) {
 			const uint32_t m = d->tri_material[i];
 			if (m != PRGPU_INVALID_ID) {
-				auto rough = [&](uint32_t id) {
-					const uint32_t kind = d->materials[id].kind;
-					return kind == PRGPU_MAT_ROUGH_CONDUCTOR || kind == PRGPU_MAT_ROUGH_DIELECTRIC || kind == PRGPU_MAT_PRINCIPLED;
-				};
-				const prgpu_material& M = d->materials[m];
-				const bool combinator	= M.kind == PRGPU_MAT_BLEND || M.kind == PRGPU_MAT_ADD; // a vertex on it runs the closures of its children
-				cls[i] = (combinator ? (rough(M.two_sided) || rough(M.thin)) : rough(m)) ? 1 : 0;
+				auto rough = [](const prgpu_material& M) { return M.kind == PRGPU_MAT_ROUGH_CONDUCTOR || M.kind == PRGPU_MAT_ROUGH_DIELECTRIC || M.kind == PRGPU_MAT_PRINCIPLED; };
+				cls[i] = prgpu_host::mix_any_leaf(d->materials, m, rough) ? 1 : 0; // a vertex on a blend / add runs the closures of the leaves of its tree
 			}
 		}
 		UP(sc.tri_class, cls);
@@ -464,24 +460,45 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 	std::vector<uint32_t> programs;
 	const bool has_expr				 = prgpu_host::compile_expressions(d, dev_spectra, programs);
 	const prgpu_spectrum* spectra_up = dev_spectra.data();
-	if (has_expr && uint64_t(d->n_spectral_table_values) + programs.size() > 0xFFFFFFFFull)
-		return fail(PRGPU_EUNSUPPORTED, "the scene's spectral tables and expression programs exceed the table array");
+	const uint64_t table_words = uint64_t(d->n_spectral_table_values) + (has_expr ? programs.size() : 0u); // the rows of the blend / add materials follow
+	std::vector<uint32_t> mix_rows;
+	{
+		uint64_t rows = 0;
+		for (uint32_t i = 0; i < d->n_materials; ++i)
+			if (prgpu_host::mat_is_combinator(d->materials[i].kind))
+				rows += prgpu_host::MIX_ROW_HEADER + prgpu_host::MIX_ROW_LEAF * uint64_t(PRGPU_MIX_MAX_LEAVES);
+		if (table_words + rows > 0xFFFFFFFFull)
+			return fail(PRGPU_EUNSUPPORTED, "the scene's spectral tables, expression programs and blend / add rows exceed the table array");
+	}
 	{
 		std::vector<prd::DevMaterial> mats(std::max<uint32_t>(1, d->n_materials));
 		std::memset(mats.data(), 0, mats.size() * sizeof(prd::DevMaterial));
 		for (uint32_t i = 0; i < d->n_materials; ++i) {
 			mats[i].m	   = d->materials[i];
 			mats[i].albedo = spectra_up[d->materials[i].albedo];
+			if (!prgpu_host::mat_is_combinator(d->materials[i].kind))
+				continue;
+			// a blend / add: its tree, flattened to one row behind the tables and the programs (host/mix_tree.h).  Its albedo is not
+			// read, so the node copy carries where the row starts and the root's delta-only bit; no record grows, DevScene does not change.
+			const prgpu_host::MixRow row = prgpu_host::mix_flatten(d->materials, i);
+			std::memset(&mats[i].albedo, 0, sizeof(mats[i].albedo));
+			mats[i].albedo.kind			= PRGPU_SPEC_CONST;
+			mats[i].albedo.table_offset = uint32_t(table_words + mix_rows.size());
+			mats[i].albedo.table_count	= row.delta_only ? 1u : 0u;
+			prgpu_host::mix_row_emit(row, mix_rows);
 		}
 		UP(sc.materials, mats);
 	}
 	UP(sc.emissions, d->emissions, d->n_emissions);
 	UP(sc.spectra, spectra_up, d->n_spectra);
-	if (has_expr) {
-		std::vector<float> tables(size_t(d->n_spectral_table_values) + programs.size());
+	if (has_expr || !mix_rows.empty()) {
+		std::vector<float> tables(size_t(table_words) + mix_rows.size());
 		if (d->n_spectral_table_values)
 			std::memcpy(tables.data(), d->spectral_tables, size_t(d->n_spectral_table_values) * sizeof(float));
-		std::memcpy(tables.data() + d->n_spectral_table_values, programs.data(), programs.size() * sizeof(uint32_t));
+		if (has_expr)
+			std::memcpy(tables.data() + d->n_spectral_table_values, programs.data(), programs.size() * sizeof(uint32_t));
+		if (!mix_rows.empty())
+			std::memcpy(tables.data() + table_words, mix_rows.data(), mix_rows.size() * sizeof(uint32_t));
 		UP(sc.tables, tables);
 	} else {
 		UP(sc.tables, d->spectral_tables, d->n_spectral_table_values);
@@ -577,7 +594,7 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 		const uint32_t kind = d->materials[i].kind;
 		if (kind == PRGPU_MAT_DIELECTRIC || kind == PRGPU_MAT_CONDUCTOR || kind == PRGPU_MAT_MIRROR)
 			sc.features |= prd::FEAT_DELTA_MATERIALS;
-		else if (kind == PRGPU_MAT_OREN_NAYAR || kind == PRGPU_MAT_NULL || kind == PRGPU_MAT_BLEND || kind == PRGPU_MAT_ADD) // the top variant only (children set their own bits)
+		else if (kind == PRGPU_MAT_OREN_NAYAR || kind == PRGPU_MAT_NULL || kind == PRGPU_MAT_BLEND || kind == PRGPU_MAT_ADD) // the top variant only (the leaves of a blend / add tree are materials of this array: they set their own bits)
 			sc.features |= prd::FEAT_MIX_MATERIALS;
 		else if (kind != PRGPU_MAT_LAMBERT) // rough closures fall back to the smooth ones below roughness 1e-3
 			sc.features |= prd::FEAT_DELTA_MATERIALS | prd::FEAT_ROUGH_MATERIALS;

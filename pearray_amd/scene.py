@@ -279,12 +279,24 @@ class SceneBuilder:
         self.materials.append(abi.Material(abi.MAT_NULL, self.spectrum_const(1.0), 0, 0, 0, 0, 0))
         return len(self.materials) - 1
 
+    def _mix_extent(self, m):
+        """(blend / add materials on the longest path below material m, leaves with a shared child counted once per path)"""
+        mat = self.materials[m]
+        if mat.kind not in (abi.MAT_BLEND, abi.MAT_ADD):
+            return 0, 1
+        (d1, n1), (d2, n2) = self._mix_extent(mat.two_sided), self._mix_extent(mat.thin)
+        return max(d1, d2) + 1, n1 + n2
+
     def _combinator(self, kind, m1, m2, factor):
         for m in (m1, m2):
             if not 0 <= m < len(self.materials):
                 raise ValueError("blend / add: child %r is not a material added before" % (m,))
-            if self.materials[m].kind in (abi.MAT_BLEND, abi.MAT_ADD):
-                raise ValueError("blend / add: a blend or add material as a child is not supported")
+        # the children may be blends / adds themselves (blend.cpp, add.cpp recurse), within the two bounds of include/prgpu.h
+        (d1, n1), (d2, n2) = self._mix_extent(m1), self._mix_extent(m2)
+        if max(d1, d2) + 1 > abi.MIX_MAX_DEPTH:
+            raise ValueError("blend / add: %d blend / add materials on a path to a leaf, more than PRGPU_MIX_MAX_DEPTH (%d)" % (max(d1, d2) + 1, abi.MIX_MAX_DEPTH))
+        if n1 + n2 > abi.MIX_MAX_LEAVES:
+            raise ValueError("blend / add: %d leaves below it, more than PRGPU_MIX_MAX_LEAVES (%d)" % (n1 + n2, abi.MIX_MAX_LEAVES))
         self.materials.append(abi.Material(kind, self.spectrum_const(1.0), m1, 0, 0, m2, 0, 0, float(factor), 0.0))
         return len(self.materials) - 1
 

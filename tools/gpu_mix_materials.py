@@ -4,10 +4,15 @@
   lambert/top  the same, plus one null material nothing uses: the scene runs the TOP variant row, as every scene with one of the four kinds does,
   orennayar    Oren-Nayar walls (roughness 0.6), Lambert blocks,
   blend        Lambert walls, blocks of blend(Lambert, rough conductor, 0.5): two closure evaluations per next event estimation,
+  nested       the same with every such blend wrapped once more, blend(null, blend(Lambert, rough conductor, 0.5), 1): what one more level costs alone
+               -- the same two leaves with the same coefficients, a sample draws one more number and takes one more step down.  (Factor 1, not 0:
+               a factor of 0 is material1 alone, blend.cpp:109, which would turn the blocks into null surfaces and time another scene.)
 rendered in ONE process, alternating, `--repeats` times `--iters` iterations each after a warm-up, timed with the host clock around work
 that ends in a device synchronise.  Prints ms per iteration (median, min .. max over the repeats) and the ratio to `lambert`.
 
-    python tools/gpu_mix_materials.py [--size 512 --spp 128 --iters 16 --repeats 5] [--out profiles/mix_materials_cost.log]
+    python tools/gpu_mix_materials.py [--size 512 --spp 128 --iters 16 --repeats 5] [--kinds lambert,blend] [--out profiles/mix_nesting_cost.log]
+
+`--kinds` leaves scenes out (`lambert` always runs: it is the unit of the ratios) -- a library from before nested trees refuses `nested`.
 """
 import argparse
 import os
@@ -45,7 +50,9 @@ def box(size, spp, kind):
     white = b.lambert(b.refl(0.7, 0.7, 0.65))
     b.add_mesh([[-0.3, -0.3, 1.98], [0.3, -0.3, 1.98], [0.3, 0.3, 1.98], [-0.3, 0.3, 1.98]], [[0, 1, 2], [0, 2, 3]], white,
                emission=b.diffuse_emission(b.smul(b.illuminant_d65(), b.illum(17, 12, 4))))
-    block = b.blend(white, b.rough_conductor(0.25), 0.5) if kind == "blend" else white
+    block = b.blend(white, b.rough_conductor(0.25), 0.5) if kind in ("blend", "nested") else white
+    if kind == "nested":
+        block = b.blend(b.null(), block, 1.0)
     for cx, cy, h in ((-0.35, 0.3, 1.2), (0.35, -0.2, 0.6)):   # two blocks
         r = 0.3
         c = [[cx - r, cy - r], [cx + r, cy - r], [cx + r, cy + r], [cx - r, cy + r]]
@@ -63,8 +70,11 @@ def main():
     ap.add_argument("--iters", type=int, default=16)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=None, help="append the result lines to this file")
+    ap.add_argument("--kinds", default=None, help="comma-separated subset of the scenes")
     a = ap.parse_args()
-    kinds = ("lambert", "lambert/top", "orennayar", "blend")
+    kinds = ("lambert", "lambert/top", "orennayar", "blend", "nested")
+    if a.kinds:
+        kinds = tuple(k for k in kinds if k == "lambert" or k in a.kinds.split(","))
     ctxs = {}
     for k in kinds:
         ctxs[k] = backend.RenderContext(box(a.size, a.spp, k), device=0)
