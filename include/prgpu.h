@@ -53,7 +53,9 @@ extern "C" {
                                prgpu_image_load came with the latter; PRGPU_MAT_OREN_NAYAR, PRGPU_MAT_NULL, PRGPU_MAT_BLEND and PRGPU_MAT_ADD are new
                                enumerators that reuse fields of prgpu_material, no field moved; PRGPU_SPEC_ADD .. PRGPU_SPEC_PEAK are new enumerators
                                that reuse lhs / rhs / p of prgpu_spectrum, no field moved; a BLEND / ADD may name a BLEND / ADD as a child
-                               (PRGPU_MIX_MAX_DEPTH, PRGPU_MIX_MAX_LEAVES) and prgpu_mix_leaves reports the flattened tree, no field moved */
+                               (PRGPU_MIX_MAX_DEPTH, PRGPU_MIX_MAX_LEAVES) and prgpu_mix_leaves reports the flattened tree, no field moved;
+                               PRGPU_SPEC_SCALAR_IMAGE .. PRGPU_SPEC_SCALAR_COS and the PRGPU_MATF_NODE_* bits are new enumerators (a bound float field holds
+                               a node index), prgpu_image_load_scalar came with them, no field moved */
 #define PRGPU_INVALID_ID 0xFFFFFFFFu /* PR_INVALID_ID, src/base/config/Constants.inl:6 */
 
 enum {
@@ -111,13 +113,35 @@ enum {
  * beyond which prgpu_scene_create answers PRGPU_EUNSUPPORTED: the operand stack a root needs (leaf 1; unary: its operand's; binary: the larger
  * of its operands', one more when they are equal) is at most PRGPU_EXPR_MAX_STACK, and a root's program (one word per node reached, a shared
  * node counted once per path to it) has at most PRGPU_EXPR_MAX_PROGRAM words.  No CHECKER or IMAGE below a math node.  An expression may
- * stand wherever MUL may (material parameters, emissions, infinite lights, CHECKER operands). */
+ * stand wherever MUL may (material parameters, emissions, infinite lights, CHECKER operands).
+ *
+ * SCALAR nodes (FloatScalarNode) live in the same array but are a family of their own: a scalar kind never stands
+ * where a spectrum is expected, nor a spectral kind where a scalar is.  A material's scalar parameter takes one through its PRGPU_MATF_NODE_*
+ * bit (below); the operands of a scalar operator are scalar kinds or CONST, the constant leaf.
+ *   SCALAR_IMAGE       ScalarImageNode of a `(texture :type 'scalar' ...)` block (src/loader/shader/ImageNode.cpp:183-241, TextureParser.cpp:198-202):
+ *                      lhs / rhs = W / H and p[0..2] as for IMAGE; table_offset = first float of W*H + 1 SINGLE floats, rows top-down, the last one 0
+ *                      (the "black" texel); table_count = W*H + 1.  A value is the file's first channel as it is (prgpu_image_load_scalar): not
+ *                      linearised, not upsampled.  Looked up at s = u, t = 1 - v on IMAGE's texel grid with its wraps; bilinear blends the four
+ *                      floats in IMAGE's order, (v00 (1-fx) + v10 fx)(1-fy) + (v01 (1-fx) + v11 fx) fy.
+ *   SCALAR_ADD .. SCALAR_COS
+ *                      the nodes of ScalarMathNode.cpp that may run on the device (`add` `sub` `mul` `div` `neg` `abs` `max` `min` `sqrt` `pow` `floor`
+ *                      `ceil` `round` `exp` `log` `sin` `cos`), fp32, a = lhs, b = rhs (unary: rhs = PRGPU_INVALID_ID): a+b, a-b, a*b, a/b, -a, |a|,
+ *                      max(a, b) = a < b ? b : a, min(a, b) = b < a ? b : a (std::max / std::min), sqrt, pow(a, b), floor, ceil, round (half away from
+ *                      zero), exp, log, sin, cos.  Operands precede the node; a SCALAR_IMAGE operand IS allowed.  Where a material binds one,
+ *                      the scene compiles it to a postfix program as it does an expression root, within the same two bounds
+ *                      (PRGPU_EXPR_MAX_STACK, PRGPU_EXPR_MAX_PROGRAM).  A tree without a SCALAR_IMAGE is a constant: the .prc loader and
+ *                      SceneBuilder fold it (all 32 names of ScalarMathNode.cpp) and write the number. */
 enum { PRGPU_SPEC_CONST = 0, PRGPU_SPEC_PARAMETRIC = 1, PRGPU_SPEC_PARAMETRIC_SCALED = 2,
        PRGPU_SPEC_TABLE = 3, PRGPU_SPEC_MUL = 4, PRGPU_SPEC_SELLMEIER = 5, PRGPU_SPEC_CHECKER = 6, PRGPU_SPEC_IMAGE = 7,
        PRGPU_SPEC_ADD = 8, PRGPU_SPEC_SUB = 9, PRGPU_SPEC_DIV = 10, PRGPU_SPEC_NEG = 11, PRGPU_SPEC_ABS = 12, PRGPU_SPEC_MAX = 13,
        PRGPU_SPEC_MIN = 14, PRGPU_SPEC_BURN = 15, PRGPU_SPEC_SCREEN = 16, PRGPU_SPEC_DODGE = 17, PRGPU_SPEC_OVERLAY = 18,
        PRGPU_SPEC_SOFTLIGHT = 19, PRGPU_SPEC_HARDLIGHT = 20, PRGPU_SPEC_BLEND = 21, PRGPU_SPEC_BRIGHTNESS_CONTRAST = 22,
-       PRGPU_SPEC_BLACKBODY = 23, PRGPU_SPEC_PEAK = 24 };
+       PRGPU_SPEC_BLACKBODY = 23, PRGPU_SPEC_PEAK = 24,
+       /* the scalar family starts at 32 (25 .. 31 are no kind: room for spectral ones, and a description that counts on from PEAK is refused) */
+       PRGPU_SPEC_SCALAR_IMAGE = 32, PRGPU_SPEC_SCALAR_ADD = 33, PRGPU_SPEC_SCALAR_SUB = 34, PRGPU_SPEC_SCALAR_MUL = 35, PRGPU_SPEC_SCALAR_DIV = 36,
+       PRGPU_SPEC_SCALAR_NEG = 37, PRGPU_SPEC_SCALAR_ABS = 38, PRGPU_SPEC_SCALAR_MAX = 39, PRGPU_SPEC_SCALAR_MIN = 40, PRGPU_SPEC_SCALAR_SQRT = 41,
+       PRGPU_SPEC_SCALAR_POW = 42, PRGPU_SPEC_SCALAR_FLOOR = 43, PRGPU_SPEC_SCALAR_CEIL = 44, PRGPU_SPEC_SCALAR_ROUND = 45, PRGPU_SPEC_SCALAR_EXP = 46,
+       PRGPU_SPEC_SCALAR_LOG = 47, PRGPU_SPEC_SCALAR_SIN = 48, PRGPU_SPEC_SCALAR_COS = 49 };
 #define PRGPU_EXPR_MAX_STACK   4  /* operand-stack entries of the device evaluator: four blobs held in registers */
 #define PRGPU_EXPR_MAX_PROGRAM 64 /* words of one root's program */
 
@@ -125,7 +149,7 @@ typedef struct prgpu_spectrum {
 	uint32_t kind;
 	float    p[4];          /* CONST: p[0]; PARAMETRIC*: a,b,c (, power) */
 	uint32_t table_offset;  /* TABLE: first sample in prgpu_scene_desc::spectral_tables; IMAGE: first float of the texels */
-	uint32_t table_count;   /* TABLE: number of samples (>= 2); IMAGE: 4 (W*H + 1) */
+	uint32_t table_count;   /* TABLE: number of samples (>= 2); IMAGE: 4 (W*H + 1); SCALAR_IMAGE: W*H + 1 */
 	float    wl_start;      /* TABLE: wavelength of first sample [nm] */
 	float    wl_end;        /* TABLE: wavelength of last sample [nm] */
 	uint32_t lhs, rhs;      /* MUL and the other math nodes: operand node indices (unary: rhs = PRGPU_INVALID_ID); CHECKER: op1 (odd cells), op2 (even cells); IMAGE: width, height */
@@ -165,7 +189,14 @@ enum { PRGPU_MAT_OREN_NAYAR = 7, PRGPU_MAT_NULL = 8, PRGPU_MAT_BLEND = 9, PRGPU_
 enum { PRGPU_MATF_ANISOTROPIC = 1u,      /* roughness_y given as its own parameter (the reference compares the NODES, not the values) */
        PRGPU_MATF_NO_VNDF = 2u,          /* `:vndf false`: sample the plain GGX normal distribution (Microfacet.h:225-256; the anisotropic form
                                             through the backend's shared fp32 tan / atan) */
-       PRGPU_MATF_HAS_TRANSMISSION = 4u }; /* PRINCIPLED: a transmission parameter was given (principled.cpp:657-666 picks the template by presence) */
+       PRGPU_MATF_HAS_TRANSMISSION = 4u, /* PRINCIPLED: a transmission parameter was given (principled.cpp:657-666 picks the template by presence) */
+       /* A scalar parameter bound to a scalar NODE (SCALAR_IMAGE or a scalar operator over one): one bit per float field of prgpu_material.
+          While a field's bit is set the field holds the node's INDEX as a float (an exactly representable integer below 2^24) instead of
+          a value; the kernels evaluate the node at the shading point's uv and put the result in the field's place.  Rough kinds: roughness_x,
+          roughness_y; OREN_NAYAR: roughness_x; PRINCIPLED: roughness_x and principled[k] (bit PRGPU_MATF_NODE_PRINCIPLED << k).  Not on BLEND's
+          factor (the tree is flattened on the host), not on sphere entities.  Without a bit the record is what it always was. */
+       PRGPU_MATF_NODE_ROUGHNESS_X = 1u << 8, PRGPU_MATF_NODE_ROUGHNESS_Y = 1u << 9, PRGPU_MATF_NODE_PRINCIPLED = 1u << 10,
+       PRGPU_MATF_NODE_MASK = 0xFFFu << 8 };
 /* PRINCIPLED scalar parameters (principled.cpp:634-655; defaults 0 except roughness 0.5 in roughness_x) */
 enum { PRGPU_PRINCIPLED_DIFFUSE_TRANSMISSION = 0, PRGPU_PRINCIPLED_SPECULAR_TRANSMISSION = 1, PRGPU_PRINCIPLED_SPECULAR_TINT = 2,
        PRGPU_PRINCIPLED_ANISOTROPIC = 3, PRGPU_PRINCIPLED_FLATNESS = 4, PRGPU_PRINCIPLED_METALLIC = 5, PRGPU_PRINCIPLED_SHEEN = 6,
@@ -181,7 +212,7 @@ typedef struct prgpu_material {
 	uint32_t thin;         /* DIELECTRIC: `thin` sheet approximation (dielectric.cpp:69-72,98-101); PRINCIPLED: `thin`; BLEND, ADD: material index of `material2` (as `material1`) */
 	uint32_t k;            /* (ROUGH_)CONDUCTOR: `k`/`kappa` absorption index spectrum (default 2.605) */
 	uint32_t flags;        /* PRGPU_MATF_* (rough kinds) */
-	float roughness_x;     /* rough kinds: `roughness_x` or `roughness` (constant scalar; textures are out of scope); OREN_NAYAR: `roughness` (default 0.5);
+	float roughness_x;     /* rough kinds: `roughness_x` or `roughness` (a number, or a scalar node's index under PRGPU_MATF_NODE_ROUGHNESS_X); OREN_NAYAR: `roughness` (default 0.5);
 	                          BLEND: `factor` as given (default 0.5; finite; clamped to [0, 1] where it is evaluated) */
 	float roughness_y;     /* rough kinds: `roughness_y`; ignored (= roughness_x) unless PRGPU_MATF_ANISOTROPIC */
 	float principled[PRGPU_PRINCIPLED_COUNT]; /* PRINCIPLED: albedo = `base`/`base_color` (default 0.8), ior (1.55), roughness_x = `roughness` (0.5),
@@ -422,6 +453,10 @@ int  prgpu_write_rgb_coeff_table(const char* path, uint32_t resolution, int thre
  * PRGPU_EINVAL, as is a damaged file (checksum, stream, filter); a missing or truncated one PRGPU_EIO.  channels_in_file and linearised
  * may be NULL.  Host only. */
 int  prgpu_image_load(const char* path, uint32_t* width, uint32_t* height, uint32_t* channels_in_file, int* linearised, float* rgb);
+/* The same files as a `(texture :type 'scalar' ...)` block reads them (ScalarImageNode): the file's FIRST channel alone (grey; R of RGB / RGBA; the
+ * red of a palette entry), integers divided by 255 / 65535, a PFM float as it is -- no linearisation.  Writes height x width floats, rows
+ * top-down, to `values`; values == NULL queries the size only.  Errors as prgpu_image_load.  Host only. */
+int  prgpu_image_load_scalar(const char* path, uint32_t* width, uint32_t* height, uint32_t* channels_in_file, float* values);
 /* The tree below material `material` as the device reads it (one table row per BLEND / ADD, compiled at scene creation): the plain leaves
  * IMaterial::eval reaches, depth first, child 1 before child 2, each with the coefficient of its weight and of its pdf -- eval of the root is
  * sum weight_i w_i and sum pdf_i p_i.  The coefficients are fp32 products formed from the root down: blend, neither child delta-only: (1 - f)

@@ -21,10 +21,25 @@ SPEC_OPS = {"smul": SPEC_MUL, "sadd": SPEC_ADD, "ssub": SPEC_SUB, "sdiv": SPEC_D
             "smin": SPEC_MIN, "sburn": SPEC_BURN, "sscreen": SPEC_SCREEN, "sdodge": SPEC_DODGE, "soverlay": SPEC_OVERLAY,
             "ssoftlight": SPEC_SOFTLIGHT, "shardlight": SPEC_HARDLIGHT, "sblend": SPEC_BLEND, "sbrightnesscontrast": SPEC_BRIGHTNESS_CONTRAST}
 EXPR_MAX_STACK, EXPR_MAX_PROGRAM = 4, 64
+# the scalar nodes (include/prgpu.h): a scalar texture and the operators of ScalarMathNode.cpp that may run on the device, in enumerator order
+(SPEC_SCALAR_IMAGE, SPEC_SCALAR_ADD, SPEC_SCALAR_SUB, SPEC_SCALAR_MUL, SPEC_SCALAR_DIV, SPEC_SCALAR_NEG, SPEC_SCALAR_ABS, SPEC_SCALAR_MAX,
+ SPEC_SCALAR_MIN, SPEC_SCALAR_SQRT, SPEC_SCALAR_POW, SPEC_SCALAR_FLOOR, SPEC_SCALAR_CEIL, SPEC_SCALAR_ROUND, SPEC_SCALAR_EXP, SPEC_SCALAR_LOG,
+ SPEC_SCALAR_SIN, SPEC_SCALAR_COS) = range(32, 50)   # (25 .. 31 are no kind)
+# name -> (device enumerator or None for a name that only folds over constants, arity): the 32 names the reference registers, and `pow`
+SCALAR_OPS = {"add": (SPEC_SCALAR_ADD, 2), "sub": (SPEC_SCALAR_SUB, 2), "subtract": (SPEC_SCALAR_SUB, 2), "mul": (SPEC_SCALAR_MUL, 2),
+              "multiply": (SPEC_SCALAR_MUL, 2), "div": (SPEC_SCALAR_DIV, 2), "divide": (SPEC_SCALAR_DIV, 2), "neg": (SPEC_SCALAR_NEG, 1),
+              "negate": (SPEC_SCALAR_NEG, 1), "sin": (SPEC_SCALAR_SIN, 1), "cos": (SPEC_SCALAR_COS, 1), "tan": (None, 1), "asin": (None, 1),
+              "acos": (None, 1), "atan": (None, 1), "sinh": (None, 1), "cosh": (None, 1), "tanh": (None, 1), "asinh": (None, 1),
+              "acosh": (None, 1), "atanh": (None, 1), "exp": (SPEC_SCALAR_EXP, 1), "log": (SPEC_SCALAR_LOG, 1), "abs": (SPEC_SCALAR_ABS, 1),
+              "sqrt": (SPEC_SCALAR_SQRT, 1), "cbrt": (None, 1), "ceil": (SPEC_SCALAR_CEIL, 1), "floor": (SPEC_SCALAR_FLOOR, 1),
+              "round": (SPEC_SCALAR_ROUND, 1), "atan2": (None, 2), "max": (SPEC_SCALAR_MAX, 2), "min": (SPEC_SCALAR_MIN, 2),
+              "pow": (SPEC_SCALAR_POW, 2)}
 MAT_LAMBERT, MAT_DIELECTRIC, MAT_CONDUCTOR, MAT_ROUGH_CONDUCTOR, MAT_ROUGH_DIELECTRIC, MAT_PRINCIPLED, MAT_MIRROR = 0, 1, 2, 3, 4, 5, 6
 MAT_OREN_NAYAR, MAT_NULL, MAT_BLEND, MAT_ADD = 7, 8, 9, 10   # BLEND / ADD: two_sided, thin = the two children's material indices, roughness_x = the blend factor
 MIX_MAX_DEPTH, MIX_MAX_LEAVES = 4, 8                         # PRGPU_MIX_MAX_DEPTH, PRGPU_MIX_MAX_LEAVES: the bounds of a BLEND / ADD tree
 MATF_ANISOTROPIC, MATF_NO_VNDF, MATF_HAS_TRANSMISSION = 1, 2, 4
+# a float field bound to a scalar node holds the node's index: roughness_x, roughness_y, principled[k] (MATF_NODE_PRINCIPLED << k)
+MATF_NODE_ROUGHNESS_X, MATF_NODE_ROUGHNESS_Y, MATF_NODE_PRINCIPLED, MATF_NODE_MASK = 1 << 8, 1 << 9, 1 << 10, 0xFFF << 8
 PRINCIPLED_PARAMS = ("diffuse_transmission", "specular_transmission", "specular_tint", "anisotropic", "flatness", "metallic", "sheen",
                      "sheen_tint", "clearcoat", "clearcoat_gloss")
 ENTITY_MESH, ENTITY_PLANE, ENTITY_SPHERE, ENTITY_QUADRIC, ENTITY_DISK = 0, 1, 2, 3, 4
@@ -186,6 +201,7 @@ SYMBOLS = {
     "prgpu_rgb_to_coeffs": (C.c_int, [_F32P, _F32P]),
     "prgpu_write_rgb_coeff_table": (C.c_int, [C.c_char_p, C.c_uint32, C.c_int]),
     "prgpu_image_load": (C.c_int, [C.c_char_p, _U32P, _U32P, _U32P, C.POINTER(C.c_int), _F32P]),
+    "prgpu_image_load_scalar": (C.c_int, [C.c_char_p, _U32P, _U32P, _U32P, _F32P]),
     "prgpu_mix_leaves": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, _U32P, _U32P, _U32P, _U32P]),
     "prgpu_scene_create": (C.c_int, [C.POINTER(SceneDesc), C.c_int, C.POINTER(_VP)]),
     "prgpu_scene_destroy": (None, [_VP]),

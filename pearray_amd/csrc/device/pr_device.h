@@ -102,7 +102,8 @@ struct DevEntity {
 constexpr uint32_t FEAT_DELTA_MATERIALS = 1u, FEAT_INFINITE_LIGHTS = 2u, FEAT_PLANES = 4u, FEAT_SPHERES = 8u, FEAT_AOVS = 16u, FEAT_SHAPE_LIGHTS = 32u, FEAT_TEXTURES = 64u,
 				   FEAT_ROUGH_MATERIALS = 128u, FEAT_LPE = 256u, FEAT_QUADRICS = 512u, FEAT_DISKS = 1024u, FEAT_IMAGES = 2048u,
 				   FEAT_MIX_MATERIALS = 4096u /* Oren-Nayar, null, blend, add (PRGPU_MAT_OREN_NAYAR ..): the top variant only */,
-				   FEAT_EXPR = 8192u /* spectral expression roots (PRGPU_SPEC_ADD ..; a program per root): the top variant only */, FEAT_ALL = 16383u;
+				   FEAT_EXPR = 8192u /* spectral expression roots (PRGPU_SPEC_ADD ..; a program per root): the top variant only */,
+				   FEAT_SCALAR_NODES = 16384u /* a material's scalar parameter is bound to a scalar node (PRGPU_MATF_NODE_*): the top variant only */, FEAT_ALL = 32767u;
 
 // QuadricEntity (src/plugins/main/entities/quadric.cpp; `quadric`, `cone`, `cylinder`): an implicit surface inside a local box.  Embree
 // sees a user geometry: one primitive with the world box as bounds and the entity's own intersect / occluded callbacks.  Here the few

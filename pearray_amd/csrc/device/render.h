@@ -70,14 +70,15 @@ void launch_path_persistent(const DevScene& sc, const PathState& ps, const uint3
 // the all-features kernel 7 % (C5 135 -> 125 Msamples/s); quadric and disk entities, image textures (FEAT_IMAGES) and the Oren-Nayar / null / blend / add
 // materials (FEAT_MIX_MATERIALS) ride in that top row (what a disk or an image scene pays for the expression hooks there has not been measured).
 // Spectral expression roots (FEAT_EXPR) ride there too, in exactly the rows that have FEAT_IMAGES: the closures'
-// _uv forms (rough_closures.inl) serve both.
+// _uv forms (rough_closures.inl) serve both.  Scalar nodes on scalar material parameters (FEAT_SCALAR_NODES) ride in
+// the top row alone: scalar_resolve writes a vertex's resolved values into its local material record, which the closures read as before.
 // A translation unit of render.hip takes its row by -DPR_VARIANT=<id>.  Adding a variant takes exactly two edits: a row here, and its id in
 // the Makefile's VARIANTS list.
 struct PathVariant {
 	int id;			   // PR_VARIANT of its translation units; bit id - 1 of PR_PL_VARIANTS
 	uint32_t features; // FEAT_* bits the kernel is compiled with
 };
-constexpr uint32_t FEAT_NO_LPE = FEAT_ALL & ~(FEAT_LPE | FEAT_QUADRICS | FEAT_DISKS | FEAT_IMAGES | FEAT_MIX_MATERIALS | FEAT_EXPR), FEAT_NO_ROUGH = FEAT_NO_LPE & ~FEAT_ROUGH_MATERIALS;
+constexpr uint32_t FEAT_NO_LPE = FEAT_ALL & ~(FEAT_LPE | FEAT_QUADRICS | FEAT_DISKS | FEAT_IMAGES | FEAT_MIX_MATERIALS | FEAT_EXPR | FEAT_SCALAR_NODES), FEAT_NO_ROUGH = FEAT_NO_LPE & ~FEAT_ROUGH_MATERIALS;
 constexpr PathVariant PATH_VARIANTS[] = { { 1, 0u }, { 2, FEAT_DELTA_MATERIALS }, { 3, FEAT_NO_ROUGH }, { 4, FEAT_NO_LPE }, { 5, FEAT_ALL } };
 constexpr int N_PATH_VARIANTS		  = int(sizeof(PATH_VARIANTS) / sizeof(PATH_VARIANTS[0]));
 // index of the scene's row

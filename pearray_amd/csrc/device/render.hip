@@ -706,6 +706,144 @@ __device__ __forceinline__ uint32_t resolve_texture(const DevScene& sc, uint32_t
 	}
 	return id;
 }
+// ---- scalar nodes (FEAT_SCALAR_NODES builds only) ---------------------------------------------------------------
+// PRGPU_SPEC_SCALAR_IMAGE (ScalarImageNode::eval, shader/ImageNode.cpp:183-241): image_eval's lookup -- s = u, t = 1 - v, the same texel
+// grid, wraps and blend order -- over single floats: the file's first channel as it is, texel W H the black one (0).  The four loads of a
+// bilinear lookup are issued before the blend.
+__device__ __forceinline__ float scalar_image_eval(const DevScene& sc, const prgpu_spectrum& n, const float uv[2])
+{
+	const int W = (int)n.lhs, H = (int)n.rhs, black = W * H;
+	const int ws = (int)n.p[1], wt = (int)n.p[2];
+	const float* __restrict__ tex = sc.tables + n.table_offset;
+	const float s = uv[0], t = 1.0f - uv[1];
+	if (n.p[0] == 0.0f) {
+		const int i = image_wrap(image_floor(s * W), W, ws), j = image_wrap(image_floor(t * H), H, wt);
+		return tex[(i < 0 || j < 0) ? black : j * W + i];
+	}
+	const float x = s * W - 0.5f, y = t * H - 0.5f;
+	const float x0 = floorf(x), y0 = floorf(y);
+	const float fx = x - x0, fy = y - y0;
+	const int ia = image_floor(x), ja = image_floor(y);
+	const int i0 = image_wrap(ia, W, ws), i1 = image_wrap(ia + 1, W, ws), j0 = image_wrap(ja, H, wt), j1 = image_wrap(ja + 1, H, wt);
+	const float v00 = tex[(i0 < 0 || j0 < 0) ? black : j0 * W + i0], v10 = tex[(i1 < 0 || j0 < 0) ? black : j0 * W + i1];
+	const float v01 = tex[(i0 < 0 || j1 < 0) ? black : j1 * W + i0], v11 = tex[(i1 < 0 || j1 < 0) ? black : j1 * W + i1];
+	return (v00 * (1.0f - fx) + v10 * fx) * (1.0f - fy) + (v01 * (1.0f - fx) + v11 * fx) * fy;
+}
+// one operator of ScalarMathNode.cpp:109-144 that runs on the device, in the reference's operand order (std::max / std::min as they compare)
+__device__ __forceinline__ float scalar_op(uint32_t kind, float a, float b)
+{
+	switch (kind) {
+	case PRGPU_SPEC_SCALAR_ADD: return a + b;
+	case PRGPU_SPEC_SCALAR_SUB: return a - b;
+	case PRGPU_SPEC_SCALAR_MUL: return a * b;
+	case PRGPU_SPEC_SCALAR_DIV: return a / b;
+	case PRGPU_SPEC_SCALAR_NEG: return -a;
+	case PRGPU_SPEC_SCALAR_ABS: return fabsf(a);
+	case PRGPU_SPEC_SCALAR_MAX: return a < b ? b : a;
+	case PRGPU_SPEC_SCALAR_MIN: return b < a ? b : a;
+	case PRGPU_SPEC_SCALAR_SQRT: return sqrtf(a);
+	case PRGPU_SPEC_SCALAR_POW: return powf(a, b);
+	case PRGPU_SPEC_SCALAR_FLOOR: return floorf(a);
+	case PRGPU_SPEC_SCALAR_CEIL: return ceilf(a);
+	case PRGPU_SPEC_SCALAR_ROUND: return roundf(a);
+	case PRGPU_SPEC_SCALAR_EXP: return expf(a);
+	case PRGPU_SPEC_SCALAR_LOG: return logf(a);
+	case PRGPU_SPEC_SCALAR_SIN: return sinf(a);
+	case PRGPU_SPEC_SCALAR_COS: return cosf(a);
+	default: return 0.0f;
+	}
+}
+// The stack machine of expr_eval over single floats: a bound operator's record names its postfix program (table_count words at word
+// table_offset of DevScene::tables; host/setup.cpp, compile_scalar_nodes), a word is a node index and EXPR_SWAP.  Four NAMED stack entries
+// that shift on a push and a pop (s0 is the top): no runtime-indexed array.  The scene bounds the depth and the program's length.
+__device__ __forceinline__ float scalar_run(const DevScene& sc, const prgpu_spectrum& root, const float uv[2])
+{
+	static_assert(PRGPU_EXPR_MAX_STACK == 4, "scalar_run keeps exactly four stack entries in registers");
+	const uint32_t* __restrict__ prog = reinterpret_cast<const uint32_t*>(sc.tables) + root.table_offset;
+	float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+#pragma unroll 1
+	for (uint32_t i = 0; i < root.table_count; ++i) {
+		const uint32_t word		= prog[i];
+		const prgpu_spectrum& n = sc.spectra[word & EXPR_NODE_MASK];
+		const uint32_t kind		= n.kind;
+		if (kind >= PRGPU_SPEC_SCALAR_ADD) {
+			const bool unary = kind != PRGPU_SPEC_SCALAR_ADD && kind != PRGPU_SPEC_SCALAR_SUB && kind != PRGPU_SPEC_SCALAR_MUL && kind != PRGPU_SPEC_SCALAR_DIV
+							   && kind != PRGPU_SPEC_SCALAR_MAX && kind != PRGPU_SPEC_SCALAR_MIN && kind != PRGPU_SPEC_SCALAR_POW;
+			const bool swap	 = (word & EXPR_SWAP) != 0u;
+			const float a = unary ? s0 : (swap ? s0 : s1), b = swap ? s1 : s0;
+			s0			  = scalar_op(kind, a, b);
+			if (!unary) {
+				s1 = s2;
+				s2 = s3;
+			}
+		} else { // a leaf: a scalar texture or the constant
+			s3 = s2;
+			s2 = s1;
+			s1 = s0;
+			s0 = kind == PRGPU_SPEC_SCALAR_IMAGE ? scalar_image_eval(sc, n, uv) : n.p[0];
+		}
+	}
+	return s0;
+}
+// FloatScalarNode::eval of the parameters of `mat` that are bound to scalar nodes (PRGPU_MATF_NODE_*: the float field holds the node's
+// index), at the shading point's uv: the results overwrite the fields of the vertex's LOCAL record, which every closure reads as it reads a
+// number's, and the bits are cleared.  One evaluation site in a loop over the set bits; the fields are named by constant index on both
+// sides of it, so the record stays in registers.  What is NOT the reference's: a value that is not finite counts as 0, a rough conductor's /
+// dielectric's roughness is held at >= 0 and the principled `anisotropic` at <= 1 -- the ranges scene creation demands of a number.
+template <uint32_t FEATS>
+__device__ __forceinline__ void scalar_resolve(const DevScene& sc, const float uv[2], prgpu_material& mat)
+{
+	if (!((FEATS & FEAT_SCALAR_NODES) && (sc.features & FEAT_SCALAR_NODES)))
+		return;
+	uint32_t bits = (mat.flags & PRGPU_MATF_NODE_MASK) >> 8;
+	if (bits == 0u)
+		return;
+	mat.flags &= ~uint32_t(PRGPU_MATF_NODE_MASK);
+	const bool rough = mat.kind == PRGPU_MAT_ROUGH_CONDUCTOR || mat.kind == PRGPU_MAT_ROUGH_DIELECTRIC;
+#pragma unroll 1
+	while (bits != 0u) {
+		const int slot = __ffs((int)bits) - 1;
+		bits &= bits - 1u;
+		float field = mat.roughness_x;
+		switch (slot) {
+		case 1: field = mat.roughness_y; break;
+		case 2: field = mat.principled[0]; break;
+		case 3: field = mat.principled[1]; break;
+		case 4: field = mat.principled[2]; break;
+		case 5: field = mat.principled[3]; break;
+		case 6: field = mat.principled[4]; break;
+		case 7: field = mat.principled[5]; break;
+		case 8: field = mat.principled[6]; break;
+		case 9: field = mat.principled[7]; break;
+		case 10: field = mat.principled[8]; break;
+		case 11: field = mat.principled[9]; break;
+		default: break;
+		}
+		const prgpu_spectrum& n = sc.spectra[(uint32_t)field]; // (validated at scene creation: a scalar node of the array)
+		float v					= n.kind == PRGPU_SPEC_SCALAR_IMAGE ? scalar_image_eval(sc, n, uv) : scalar_run(sc, n, uv);
+		if (!(fabsf(v) <= 3.402823466e+38f))
+			v = 0.0f;
+		if (rough && slot < 2)
+			v = fmaxf(v, 0.0f);
+		if (slot == 2 + PRGPU_PRINCIPLED_ANISOTROPIC)
+			v = fminf(v, 1.0f);
+		switch (slot) {
+		case 0: mat.roughness_x = v; break;
+		case 1: mat.roughness_y = v; break;
+		case 2: mat.principled[0] = v; break;
+		case 3: mat.principled[1] = v; break;
+		case 4: mat.principled[2] = v; break;
+		case 5: mat.principled[3] = v; break;
+		case 6: mat.principled[4] = v; break;
+		case 7: mat.principled[5] = v; break;
+		case 8: mat.principled[6] = v; break;
+		case 9: mat.principled[7] = v; break;
+		case 10: mat.principled[8] = v; break;
+		case 11: mat.principled[9] = v; break;
+		default: break;
+		}
+	}
+}
 struct GeomPoint {
 	V3 N, Nx, Ny;
 	uint32_t entity, prim, material, emission;
@@ -1598,6 +1736,7 @@ __device__ __forceinline__ void mix_child(const DevScene& sc, uint32_t id, const
 		m.k			   = resolve_texture(sc, m.k, uv);
 		m.transmission = resolve_texture(sc, m.transmission, uv);
 	}
+	scalar_resolve<FEATS>(sc, uv, m); // (a leaf's scalar parameters may be bound to scalar nodes)
 	rough  = (FEATS & FEAT_ROUGH_MATERIALS) && (m.kind == PRGPU_MAT_ROUGH_CONDUCTOR || m.kind == PRGPU_MAT_ROUGH_DIELECTRIC || m.kind == PRGPU_MAT_PRINCIPLED);
 	albedo = rough ? blob(0) : albedo_eval<(FEATS & FEAT_IMAGES) != 0u, (FEATS & FEAT_EXPR) != 0u>(sc, m, dm.albedo, dm.m.albedo, wl, uv);
 }
@@ -2018,6 +2157,7 @@ __device__ __forceinline__ void shade_vertex(const DevScene& sc, const PathState
 				mat.k			 = resolve_texture(sc, mat.k, gp.uv);
 				mat.transmission = resolve_texture(sc, mat.transmission, gp.uv);
 			}
+			scalar_resolve<FEATS>(sc, gp.uv, mat); // scalar parameters bound to scalar nodes: their values at the point, into the local record
 			const V3 Vt				 = to_tangent_space(N, gp.Nx, gp.Ny, -ray_d);
 			uint64_t rnd			 = ps.rng[pixel];
 			const bool deltaMat		 = (FEATS & FEAT_DELTA_MATERIALS) && (mat.kind == PRGPU_MAT_DIELECTRIC || mat.kind == PRGPU_MAT_CONDUCTOR || mat.kind == PRGPU_MAT_MIRROR); // IMaterial::hasOnlyDeltaDistribution

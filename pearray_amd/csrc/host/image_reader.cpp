@@ -60,7 +60,7 @@ uint8_t paeth(int a, int b, int c)
 	return uint8_t(pa <= pb && pa <= pc ? a : (pb <= pc ? b : c));
 }
 
-int read_png(const std::vector<uint8_t>& file, Image& img, bool header_only, std::string& err)
+int read_png(const std::vector<uint8_t>& file, Image& img, bool header_only, bool scalar, std::string& err)
 {
 	size_t pos = 8;
 	bool have_header = false, have_end = false;
@@ -155,12 +155,23 @@ int read_png(const std::vector<uint8_t>& file, Image& img, bool header_only, std
 			cur[i]		  = uint8_t(cur[i] + add);
 		}
 	}
-	img.rgb.resize(size_t(img.width) * img.height * 3);
+	img.rgb.resize(size_t(uint64_t(img.width) * img.height * (scalar ? 1u : 3u)));
 	const float scale = depth == 8 ? 255.0f : 65535.0f;
 	for (uint64_t y = 0; y < img.height; ++y) {
 		const uint8_t* cur = &raw[size_t(y * (stride + 1)) + 1];
 		for (uint64_t x = 0; x < img.width; ++x) {
 			const uint8_t* px = cur + x * bpp;
+			if (scalar) { // the file's first channel as it is (a palette image: the entry's red), no linearisation
+				float& value = img.rgb[size_t(y * img.width + x)];
+				if (colour == 3) {
+					if (size_t(px[0]) * 3 + 2 >= palette.size())
+						return fail(err, PRGPU_EINVAL, "png: palette index out of range");
+					value = palette[size_t(px[0]) * 3] / 255.0f;
+				} else {
+					value = float(depth == 8 ? uint32_t(px[0]) : ((uint32_t(px[0]) << 8) | px[1])) / scale;
+				}
+				continue;
+			}
 			float* out		  = &img.rgb[size_t(y * img.width + x) * 3];
 			if (colour == 3) {
 				if (size_t(px[0]) * 3 + 2 >= palette.size())
@@ -192,7 +203,7 @@ bool pfm_token(const std::vector<uint8_t>& file, size_t& pos, std::string& tok)
 	return !tok.empty() && pos < file.size() && space(file[pos]);
 }
 
-int read_pfm(const std::vector<uint8_t>& file, Image& img, bool header_only, std::string& err)
+int read_pfm(const std::vector<uint8_t>& file, Image& img, bool header_only, bool scalar, std::string& err)
 {
 	size_t pos = 0;
 	std::string magic, ws, hs, ss;
@@ -221,18 +232,19 @@ int read_pfm(const std::vector<uint8_t>& file, Image& img, bool header_only, std
 	if (need > file.size() - pos)
 		return fail(err, PRGPU_EIO, "pfm: file ends inside the pixel data (truncated)");
 	const bool little = scale < 0.0;
-	img.rgb.resize(size_t(w * h * 3));
+	const uint32_t out_ch = scalar ? 1u : 3u; // scalar: the file's first channel alone
+	img.rgb.resize(size_t(w * h * out_ch));
 	for (uint64_t y = 0; y < h; ++y) { // the file's rows run bottom-up
 		const uint8_t* row = &file[pos + size_t((h - 1 - y) * w * ch * 4)];
 		for (uint64_t x = 0; x < w; ++x)
-			for (uint32_t k = 0; k < 3; ++k) {
+			for (uint32_t k = 0; k < out_ch; ++k) {
 				const uint8_t* b = row + (x * ch + (ch == 3 ? k : 0u)) * 4;
 				const uint32_t u = little ? (uint32_t(b[0]) | (uint32_t(b[1]) << 8) | (uint32_t(b[2]) << 16) | (uint32_t(b[3]) << 24)) : be32(b);
 				float v;
 				std::memcpy(&v, &u, 4);
 				if (!std::isfinite(v))
 					return fail(err, PRGPU_EINVAL, "pfm: a sample is not finite");
-				img.rgb[size_t(y * w + x) * 3 + k] = v;
+				img.rgb[size_t(y * w + x) * out_ch + k] = v;
 			}
 	}
 	return PRGPU_OK;
@@ -241,7 +253,7 @@ int read_pfm(const std::vector<uint8_t>& file, Image& img, bool header_only, std
 
 float image_linearise(float x) { return (x <= 0.04045f) ? x / 12.92f * x : std::pow((x + 0.055f) / 1.055f, 2.4f); }
 
-int read_image(const char* path, Image& img, bool header_only, std::string& err)
+int read_image(const char* path, Image& img, bool header_only, std::string& err, bool scalar)
 {
 	img = Image();
 	std::vector<uint8_t> file;
@@ -250,13 +262,15 @@ int read_image(const char* path, Image& img, bool header_only, std::string& err)
 	static const uint8_t png_magic[8] = { 0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A };
 	int rc;
 	if (file.size() >= 8 && std::memcmp(file.data(), png_magic, 8) == 0)
-		rc = read_png(file, img, header_only, err);
+		rc = read_png(file, img, header_only, scalar, err);
 	else if (file.size() >= 3 && file[0] == 'P' && (file[1] == 'F' || file[1] == 'f') && (file[2] == '\n' || file[2] == ' ' || file[2] == '\r' || file[2] == '\t'))
-		rc = read_pfm(file, img, header_only, err);
+		rc = read_pfm(file, img, header_only, scalar, err);
 	else if (file.size() < 8)
 		rc = fail(err, PRGPU_EIO, "image file is shorter than a signature (truncated)");
 	else
 		rc = fail(err, PRGPU_EUNSUPPORTED, "image is neither a PNG nor a PFM file");
+	if (scalar)
+		img.linearised = false;
 	if (rc != PRGPU_OK) {
 		err = std::string("image '") + path + "': " + err;
 		img = Image();
@@ -283,5 +297,24 @@ extern "C" int prgpu_image_load(const char* path, uint32_t* width, uint32_t* hei
 		*linearised = img.linearised ? 1 : 0;
 	if (rgb)
 		std::memcpy(rgb, img.rgb.data(), img.rgb.size() * sizeof(float));
+	return PRGPU_OK;
+}
+
+extern "C" int prgpu_image_load_scalar(const char* path, uint32_t* width, uint32_t* height, uint32_t* channels_in_file, float* values)
+{
+	using namespace prgpu_host;
+	if (!path || !width || !height)
+		return set_last_error(PRGPU_EINVAL, "prgpu_image_load_scalar: null argument");
+	Image img;
+	std::string err;
+	const int rc = read_image(path, img, values == nullptr, err, true);
+	if (rc != PRGPU_OK)
+		return set_last_error(rc, "prgpu_image_load_scalar: " + err);
+	*width	= img.width;
+	*height = img.height;
+	if (channels_in_file)
+		*channels_in_file = img.channels_in_file;
+	if (values)
+		std::memcpy(values, img.rgb.data(), img.rgb.size() * sizeof(float));
 	return PRGPU_OK;
 }

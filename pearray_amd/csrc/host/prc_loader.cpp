@@ -23,6 +23,7 @@
 #include <cstring>
 #include <fstream>
 #include <map>
+#include <set>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -36,6 +37,7 @@
 #include "image_reader.h"
 #include "mix_tree.h"
 #include "setup.h"
+#include "scalar_node.h"
 #include "spectral_expr.h"
 
 using prgpu_host::dl::Group;
@@ -470,6 +472,8 @@ struct Loader {
 		}
 		if (id == "spd") // SPDFilePlugin::create (node/SPDFileNode.cpp:20-91): an equidistant spectrum from a CSV file
 			return spectrum_spd_file(e);
+		if (prgpu_host::scalar_op_by_name(id)) // (the reference splats it over the wavelengths, SplatSpectralNode: not built)
+			fail(PRGPU_EUNSUPPORTED, where(e) + ": a scalar node ('" + id + "') where a spectrum is expected is not supported");
 		fail(PRGPU_EUNSUPPORTED, "spectral expression " + where(e) + " is not supported (number, refl, illum, illuminant, spectrum, spd, smul, lookup_index, checkerboard are)");
 	}
 	// CSV::read (base/container/CSV.cpp:52-163): ',' or ';' separate, empty tokens are skipped, a first row with a non-number is the
@@ -672,10 +676,17 @@ struct Loader {
 			warn(where(g) + ": no valid type given for texture '" + name + "': assuming color");
 			type = "color";
 		}
-		if (texture_ids.count(name))
+		if (texture_ids.count(name) || names_scalar(name))
 			fail(PRGPU_EINVAL, where(g) + ": texture '" + name + "' already exists");
-		if (type == "scalar")
-			fail(PRGPU_EUNSUPPORTED, where(g) + ": texture '" + name + "': scalar textures are not supported");
+		if (type == "scalar") { // ScalarImageNode (TextureParser.cpp:198-202): the file's first channel as it is
+			prgpu_host::Image img;
+			std::string err;
+			if (const int rc = prgpu_host::read_image(path.c_str(), img, false, err, true))
+				fail(rc, where(g) + ": texture '" + name + "': " + err);
+			scalar_texture_ids[name]   = scalar_image(img.rgb.data(), img.width, img.height, interpolation, wrap[0], wrap[1]);
+			scalar_texture_where[name] = where(g);
+			return;
+		}
 		if (type != "color" && type != "grayscale" && type != "spectral")
 			fail(PRGPU_EINVAL, where(g) + ": no known type given for texture '" + name + "'");
 		prgpu_host::Image img;
@@ -695,7 +706,7 @@ struct Loader {
 		if (!nv || nv->type != Value::STRING)
 			fail(PRGPU_EINVAL, where(g) + ": node without a name");
 		const std::string name = nv->s;
-		if (node_ids.count(name) || texture_ids.count(name)) // (hasNode: textures are nodes too)
+		if (node_ids.count(name) || texture_ids.count(name) || names_scalar(name)) // (hasNode: textures are nodes too)
 			fail(PRGPU_EINVAL, where(g) + ": node '" + name + "' already exists");
 		if (!tv || tv->type != Value::STRING)
 			fail(PRGPU_EINVAL, where(g) + ": no type given for node '" + name + "'");
@@ -703,7 +714,8 @@ struct Loader {
 		static const char* const known[] = { "refl", "reflection", "illum", "illumination", "illuminant", "spectrum", "spd", "checkerboard", "grid", "lookup_index", "sellmeier_index",
 											 "smul", "sadd", "ssub", "sdiv", "sneg", "sabs", "smax", "smin", "sburn", "sscreen", "sdodge", "soverlay", "ssoftlight", "shardlight",
 											 "sblend", "sbrightnesscontrast", "blackbody", "triangle_peak", "peak" };
-		if (std::find_if(std::begin(known), std::end(known), [&](const char* k) { return type == k; }) == std::end(known))
+		const bool scalar_type = prgpu_host::scalar_op_by_name(type) != nullptr; // the names of ScalarMathNode.cpp
+		if (!scalar_type && std::find_if(std::begin(known), std::end(known), [&](const char* k) { return type == k; }) == std::end(known))
 			fail(PRGPU_EUNSUPPORTED, where(g) + ": block is not supported by this backend yet");
 		// the block's parameters are the inline form's (populateObjectParameters: positional and named alike): the same group under the type's id
 		Value v;
@@ -714,10 +726,131 @@ struct Loader {
 		for (const auto& entry : g.entries)
 			if (entry.key != "name" && entry.key != "type")
 				v.g->entries.push_back(entry);
+		if (scalar_type) {
+			scalar_node_ids[name] = scalar_lookup(v, g, "node", 0.0f);
+			return;
+		}
 		const float keep = string_default; // (a math node's operands set their own default, 0; a checkerboard's theirs)
 		string_default	 = 0.0f;
 		node_ids[name]	 = spectral_node(v, g, "node");
 		string_default	 = keep;
+	}
+	// ---- scalar nodes: lookupScalarNode (SceneLoadContext.cpp:236-266), ScalarMathPlugin::create (ScalarMathNode.cpp:148-217) -----------------
+	// What a scalar parameter resolves to: a number -- a tree without a texture below it is a constant and is folded here in fp32, so the
+	// record is the number's -- or a scalar node of out.spectra (a scalar texture, or an operator with one below it: scalar_node.h).
+	struct ScalarValue {
+		bool node	= false;
+		float value = 0.0f;
+		uint32_t id = PRGPU_INVALID_ID;
+	};
+	static ScalarValue scalar_constant(float v)
+	{
+		ScalarValue r;
+		r.value = v;
+		return r;
+	}
+	std::map<std::string, uint32_t> scalar_texture_ids;	   // name -> the PRGPU_SPEC_SCALAR_IMAGE node of a (texture :type 'scalar') block
+	std::map<std::string, ScalarValue> scalar_node_ids;	   // name -> what a (node ...) block of a scalar type declared
+	std::map<std::string, std::string> scalar_texture_where; // name -> where its block stands (for the refusal of one that nothing names)
+	std::set<std::string> scalar_texture_used;			   // the scalar textures a parameter or an operand named
+	std::vector<prgpu_host::ScalarInfo> scalar_info;	   // per node of out.spectra: the two bounds of the device evaluator
+	bool names_scalar(const std::string& name) const { return scalar_texture_ids.count(name) || scalar_node_ids.count(name); }
+	// the node of a scalar image (height x width floats, rows top-down): one float per pixel, then the black texel
+	uint32_t scalar_image(const float* values, uint32_t w, uint32_t h, int interpolation, int wrap_s, int wrap_t)
+	{
+		prgpu_spectrum s = blank(PRGPU_SPEC_SCALAR_IMAGE);
+		s.lhs			 = w;
+		s.rhs			 = h;
+		s.p[0]			 = (float)interpolation;
+		s.p[1]			 = (float)wrap_s;
+		s.p[2]			 = (float)wrap_t;
+		const uint64_t n = uint64_t(w) * h + 1;
+		if (uint64_t(out.tables.size()) + n > 0xFFFFFFFFull)
+			fail(PRGPU_EUNSUPPORTED, "the scene's image textures exceed the table array");
+		s.table_offset = (uint32_t)out.tables.size();
+		s.table_count  = (uint32_t)n;
+		out.tables.insert(out.tables.end(), values, values + (n - 1));
+		out.tables.push_back(0.0f);
+		return add_spectrum(s);
+	}
+	// lookupScalarNode of one parameter value; `def` is what a value that names no scalar node yields
+	ScalarValue scalar_lookup(const Value& v, const Group& owner, const char* key, float def)
+	{
+		if (v.is_number())
+			return scalar_constant((float)v.number());
+		if (v.type == Value::STRING) {
+			const auto tex = scalar_texture_ids.find(v.s);
+			if (tex != scalar_texture_ids.end()) {
+				scalar_texture_used.insert(v.s);
+				ScalarValue r;
+				r.node = true;
+				r.id   = tex->second;
+				return r;
+			}
+			const auto node = scalar_node_ids.find(v.s);
+			if (node != scalar_node_ids.end())
+				return node->second;
+			const bool other = texture_ids.count(v.s) || node_ids.count(v.s);
+			warn(std::string(":") + key + " of " + where(owner) + (other ? " names the node '" + v.s + "', which is not a scalar node" : " names the unknown node '" + v.s + "'") + ": default value used (as the reference does)");
+			return scalar_constant(def);
+		}
+		if (v.type != Value::GROUP || v.g->is_array) // (an array, a bool, nothing: the default)
+			return scalar_constant(def);
+		const Group& e		 = *v.g;
+		const std::string id = lower(e.id);
+		if (id == "perlin" || id == "noise" || id == "expr")
+			fail(PRGPU_EUNSUPPORTED, where(e) + ": the scalar node '" + id + "' is not supported");
+		const prgpu_host::ScalarOpName* op = prgpu_host::scalar_op_by_name(id);
+		if (!op) { // a reference to a node that is not scalar: the default (SceneLoadContext.cpp:248-254)
+			warn(std::string(":") + key + " of " + where(owner) + ": '" + id + "' is not a scalar node: default value used (as the reference does)");
+			return scalar_constant(def);
+		}
+		const ScalarValue a = scalar_lookup(e.at(0), e, op->arity == 2 ? "op1" : "op", 0.0f);
+		const ScalarValue b = op->arity == 2 ? scalar_lookup(e.at(1), e, "op2", 0.0f) : scalar_constant(0.0f);
+		if (!a.node && !b.node)
+			return scalar_constant(prgpu_host::scalar_fold(id, a.value, b.value));
+		if (op->kind == 0)
+			fail(PRGPU_EUNSUPPORTED, where(e) + ": a dynamic '" + id
+										 + "' (over a scalar texture) is not supported: the device evaluates add sub mul div neg abs max min sqrt pow floor ceil round exp log sin cos; every name folds over constants");
+		prgpu_spectrum s = blank(op->kind);
+		s.lhs			 = a.node ? a.id : spectrum_const(a.value);
+		s.rhs			 = op->arity == 2 ? (b.node ? b.id : spectrum_const(b.value)) : PRGPU_INVALID_ID;
+		ScalarValue r;
+		r.node = true;
+		r.id   = add_spectrum(s);
+		scalar_info.resize(r.id);
+		scalar_info.push_back(prgpu_host::scalar_info_of(s, scalar_info));
+		if (scalar_info[r.id].need > PRGPU_EXPR_MAX_STACK)
+			fail(PRGPU_EUNSUPPORTED, where(e) + ": the scalar expression needs an operand stack of " + std::to_string(scalar_info[r.id].need) + " entries, more than the device evaluator's "
+										 + std::to_string(PRGPU_EXPR_MAX_STACK) + " (PRGPU_EXPR_MAX_STACK)");
+		if (scalar_info[r.id].length > PRGPU_EXPR_MAX_PROGRAM)
+			fail(PRGPU_EUNSUPPORTED, where(e) + ": the scalar expression's program is longer than the device evaluator's " + std::to_string(PRGPU_EXPR_MAX_PROGRAM) + " words (PRGPU_EXPR_MAX_PROGRAM)");
+		return r;
+	}
+	// A material's scalar parameter `key` into float field `slot` of `m` (scalar_node.h): a number; an inline group; or a string that names a
+	// scalar node.  NOT the reference's: a string that names no scalar node is refused here as it always was -- lookupScalarNode would quietly
+	// render the parameter's default in place of a mistyped roughness map.  (Operands of a math node do follow the reference: default 0.)
+	void scalar_param(prgpu_material& m, int slot, const Group& g, const char* key, float def, const char* what)
+	{
+		const Value* v	= g.get(key);
+		float& field	= prgpu_host::scalar_slot_field(m, slot);
+		if (!v) {
+			field = def;
+			return;
+		}
+		if (v->type == Value::STRING && !names_scalar(v->s))
+			fail(PRGPU_EUNSUPPORTED, where(g) + ": :" + key + " must be a number or a scalar node (" + what + " '" + v->s + "' names no scalar texture or scalar node block)");
+		if (!v->is_number() && v->type != Value::STRING && !(v->type == Value::GROUP && !v->g->is_array))
+			fail(PRGPU_EUNSUPPORTED, where(g) + ": :" + key + " must be a number or a scalar node");
+		const ScalarValue r = scalar_lookup(*v, g, key, def);
+		if (!r.node) {
+			field = r.value;
+			return;
+		}
+		if (r.id >= (1u << 24))
+			fail(PRGPU_EUNSUPPORTED, where(g) + ": a scene with scalar nodes holds at most 2^24 - 1 nodes");
+		field = (float)r.id; // the node's index while the field's bit is set (include/prgpu.h, PRGPU_MATF_NODE_*)
+		m.flags |= prgpu_host::scalar_slot_bit(slot);
 	}
 	// an image texture, or a checkerboard that holds one
 	bool holds_image(uint32_t id, int depth = 0) const
@@ -1264,21 +1397,14 @@ struct Loader {
 		prgpu_material m;
 		std::memset(&m, 0, sizeof(m));
 		const bool has_roughness = g.get("roughness") || g.get("roughness_x") || g.get("roughness_y");
-		auto roughness			 = [&](prgpu_material& mm) { // roughconductor.cpp:158-177 / roughdielectric.cpp:282-310 (scalar nodes: constants only)
-			auto scalar = [&](const char* key) -> float {
-				const Value* v = g.get(key);
-				if (!v)
-					return 0.0f; // lookupScalarNode(key, 0)
-				if (!v->is_number())
-					fail(PRGPU_EUNSUPPORTED, where(g) + ": :" + key + " must be a number (textured roughness is not supported)");
-				return (float)v->number();
-			};
-			mm.roughness_x = g.get("roughness_x") ? scalar("roughness_x") : scalar("roughness");
+		auto roughness			 = [&](prgpu_material& mm) { // roughconductor.cpp:158-177 / roughdielectric.cpp:282-310
+			// lookupScalarNode(key, 0): a number, or a scalar node (its index, under the field's PRGPU_MATF_NODE_* bit)
+			scalar_param(mm, 0, g, g.get("roughness_x") ? "roughness_x" : "roughness", 0.0f, "the string");
 			if (g.get("roughness_y")) { // its own node: the anisotropic closure, whatever the value
-				mm.roughness_y = scalar("roughness_y");
+				scalar_param(mm, 1, g, "roughness_y", 0.0f, "the string");
 				mm.flags |= PRGPU_MATF_ANISOTROPIC;
 			} else {
-				mm.roughness_y = mm.roughness_x;
+				mm.roughness_y = mm.roughness_x; // (not read without the flag)
 			}
 			if (!get_bool(g, "vndf", true))
 				mm.flags |= PRGPU_MATF_NO_VNDF;
@@ -1310,32 +1436,34 @@ struct Loader {
 			m.k			   = spectral_param(g, { "k", "kappa" }, 2.605f);
 			m.albedo	   = spectral_param(g, { "specularity" }, 1.0f);
 			m.transmission = PRGPU_INVALID_ID;
-		} else if (type == "principled") { // principled.cpp:634-687 (scalar nodes: constants only)
+		} else if (type == "principled") { // principled.cpp:634-687
 			m.kind		   = PRGPU_MAT_PRINCIPLED;
 			m.albedo	   = spectral_param(g, { "base_color", "base" }, 0.8f);
 			m.ior		   = spectral_param(g, { "ior", "eta", "index" }, 1.55f);
 			m.transmission = PRGPU_INVALID_ID;
 			m.thin		   = get_bool(g, "thin", false) ? 1 : 0;
-			auto scalar	   = [&](std::initializer_list<const char*> keys, float def) -> float {
-				   for (const char* key : keys)
-					   if (const Value* v = g.get(key)) {
-						   if (!v->is_number())
-							   fail(PRGPU_EUNSUPPORTED, where(g) + ": :" + key + " must be a number (textured principled parameters are not supported)");
-						   return (float)v->number();
-					   }
-				   return def;
+			// the first key present; a number, or a scalar node (its index, under the field's PRGPU_MATF_NODE_* bit)
+			auto scalar = [&](int slot, std::initializer_list<const char*> keys, float def) {
+				const char* key = *keys.begin();
+				for (const char* k : keys)
+					if (g.get(k)) {
+						key = k;
+						break;
+					}
+				scalar_param(m, slot, g, key, def, "the string");
 			};
-			m.roughness_x = m.roughness_y						= scalar({ "roughness" }, 0.5f);
-			m.principled[PRGPU_PRINCIPLED_DIFFUSE_TRANSMISSION]	= scalar({ "diffuse_transmission", "diff_trans" }, 0.0f);
-			m.principled[PRGPU_PRINCIPLED_SPECULAR_TRANSMISSION] = scalar({ "specular_transmission", "spec_trans" }, 0.0f);
-			m.principled[PRGPU_PRINCIPLED_SPECULAR_TINT]		= scalar({ "specular_tint" }, 0.0f);
-			m.principled[PRGPU_PRINCIPLED_ANISOTROPIC]			= scalar({ "anisotropic" }, 0.0f);
-			m.principled[PRGPU_PRINCIPLED_FLATNESS]				= scalar({ "flatness", "subsurface" }, 0.0f);
-			m.principled[PRGPU_PRINCIPLED_METALLIC]				= scalar({ "metallic" }, 0.0f);
-			m.principled[PRGPU_PRINCIPLED_SHEEN]				= scalar({ "sheen" }, 0.0f);
-			m.principled[PRGPU_PRINCIPLED_SHEEN_TINT]			= scalar({ "sheen_tint" }, 0.0f);
-			m.principled[PRGPU_PRINCIPLED_CLEARCOAT]			= scalar({ "clearcoat" }, 0.0f);
-			m.principled[PRGPU_PRINCIPLED_CLEARCOAT_GLOSS]		= scalar({ "clearcoat_gloss" }, 0.0f);
+			scalar(0, { "roughness" }, 0.5f);
+			m.roughness_y = m.roughness_x; // (not read)
+			scalar(2 + PRGPU_PRINCIPLED_DIFFUSE_TRANSMISSION, { "diffuse_transmission", "diff_trans" }, 0.0f);
+			scalar(2 + PRGPU_PRINCIPLED_SPECULAR_TRANSMISSION, { "specular_transmission", "spec_trans" }, 0.0f);
+			scalar(2 + PRGPU_PRINCIPLED_SPECULAR_TINT, { "specular_tint" }, 0.0f);
+			scalar(2 + PRGPU_PRINCIPLED_ANISOTROPIC, { "anisotropic" }, 0.0f);
+			scalar(2 + PRGPU_PRINCIPLED_FLATNESS, { "flatness", "subsurface" }, 0.0f);
+			scalar(2 + PRGPU_PRINCIPLED_METALLIC, { "metallic" }, 0.0f);
+			scalar(2 + PRGPU_PRINCIPLED_SHEEN, { "sheen" }, 0.0f);
+			scalar(2 + PRGPU_PRINCIPLED_SHEEN_TINT, { "sheen_tint" }, 0.0f);
+			scalar(2 + PRGPU_PRINCIPLED_CLEARCOAT, { "clearcoat" }, 0.0f);
+			scalar(2 + PRGPU_PRINCIPLED_CLEARCOAT_GLOSS, { "clearcoat_gloss" }, 0.0f);
 			if (g.get("specular_transmission") || g.get("spec_trans") || g.get("diffuse_transmission") || g.get("diff_trans")) // :657-666
 				m.flags |= PRGPU_MATF_HAS_TRANSMISSION;
 			if (!get_bool(g, "vndf", true)) // PrincipledMaterialPlugin::create (principled.cpp:677-685)
@@ -1347,13 +1475,7 @@ struct Loader {
 		} else if (type == "orennayar" || type == "oren" || type == "rough") { // orennayar.cpp:99-111; create() reads `albedo` only, whatever its specification lists
 			m.kind	 = PRGPU_MAT_OREN_NAYAR;
 			m.albedo = spectral_param(g, { "albedo" }, 1.0f);
-			if (const Value* v = g.get("roughness")) {
-				if (!v->is_number())
-					fail(PRGPU_EUNSUPPORTED, where(g) + ": :roughness must be a number (textured roughness is not supported)");
-				m.roughness_x = (float)v->number();
-			} else {
-				m.roughness_x = 0.5f;
-			}
+			scalar_param(m, 0, g, "roughness", 0.5f, "the string"); // a number, or a scalar node (its index, under PRGPU_MATF_NODE_ROUGHNESS_X)
 		} else if (type == "null") { // null.cpp:68-79: no parameters
 			m.kind	 = PRGPU_MAT_NULL;
 			m.albedo = spectral_param(g, {}, 1.0f);
@@ -1382,7 +1504,7 @@ struct Loader {
 			if (m.kind == PRGPU_MAT_BLEND) {
 				if (const Value* v = g.get("factor")) {
 					if (!v->is_number())
-						fail(PRGPU_EUNSUPPORTED, where(g) + ": :factor must be a number (a textured factor is not supported)");
+						fail(PRGPU_EUNSUPPORTED, where(g) + ": :factor must be a number (a scalar node on a blend's :factor is not supported: the tree is flattened on the host)");
 					m.roughness_x = (float)v->number(); // kept as given: clamped to [0, 1] where it is evaluated (blend.cpp:54,109)
 				} else {
 					m.roughness_x = 0.5f;
@@ -1604,6 +1726,8 @@ struct Loader {
 				const prgpu_material& m = out.materials[mat];
 				if (holds_image(m.albedo) || holds_image(m.ior) || holds_image(m.k) || holds_image(m.transmission))
 					fail(PRGPU_EUNSUPPORTED, where(g) + ": image textures on sphere entities are not supported (their uv needs atan2 / acos)");
+				if (prgpu_host::mix_any_leaf(out.materials.data(), mat, [](const prgpu_material& mm) { return (mm.flags & PRGPU_MATF_NODE_MASK) != 0u; }))
+					fail(PRGPU_EUNSUPPORTED, where(g) + ": scalar textures on sphere entities are not supported (their uv needs atan2 / acos)");
 			}
 			out.tri_material.push_back(mat);
 			out.entities.push_back(e);
@@ -2286,6 +2410,11 @@ struct Loader {
 			out.entities.push_back(e);
 			warn("the scene has no entities: every camera ray sees the background");
 		}
+		// A scalar texture is built for the scalar parameters that name it.  One that nothing names stays refused, as every scalar texture was:
+		// it would ride in the table array and be read by no kernel.  (NOT the reference's, which keeps an unused node silently.)
+		for (const auto& t : scalar_texture_where)
+			if (!scalar_texture_used.count(t.first))
+				fail(PRGPU_EUNSUPPORTED, t.second + ": texture '" + t.first + "': scalar textures are not supported where no scalar parameter or scalar node names them (nothing names this one)");
 		if (any_normals)
 			out.normals.resize(out.positions.size(), 0.0f);
 		if (any_uvs)

@@ -14,6 +14,7 @@
 #include "setup.h"
 #include "mix_tree.h"
 #include "spectral_expr.h"
+#include "scalar_node.h"
 
 #include <algorithm>
 #include <array>
@@ -1117,10 +1118,57 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 	}
 	std::vector<ExprInfo> expr_info; // per node, from its operands' (spectral_expr.h)
 	expr_info.reserve(d->n_spectra);
+	std::vector<ScalarInfo> scalar_info; // the same for the scalar nodes (scalar_node.h)
+	scalar_info.reserve(d->n_spectra);
 	for (uint32_t i = 0; i < d->n_spectra; ++i) {
 		const prgpu_spectrum& n = d->spectra[i];
-		if (n.kind > PRGPU_SPEC_PEAK)
+		if (n.kind > PRGPU_SPEC_SCALAR_COS || (n.kind > PRGPU_SPEC_PEAK && n.kind < PRGPU_SPEC_SCALAR_IMAGE))
 			return bad("unknown spectrum kind");
+		scalar_info.push_back(scalar_info_of(n, scalar_info));
+		if (scalar_is_kind(n.kind)) { // the scalar nodes: a family of their own (include/prgpu.h)
+			const std::string what = "scalar node " + std::to_string(i);
+			if (d->n_spectra > 0x00FFFFFFu)
+				return bad("a scene with scalar nodes holds at most 2^24 - 1 nodes", PRGPU_EUNSUPPORTED);
+			if (n.kind == PRGPU_SPEC_SCALAR_IMAGE) {
+				if (n.lhs == 0 || n.rhs == 0 || n.lhs > 4096 || n.rhs > 4096)
+					return bad("scalar image texture: width and height must be 1..4096");
+				const uint64_t need = uint64_t(n.lhs) * n.rhs + 1;
+				if (n.table_count != need || !d->spectral_tables || uint64_t(n.table_offset) + need > d->n_spectral_table_values)
+					return bad("scalar image texture: W H + 1 floats inside spectral_tables");
+				if (!(n.p[0] == 0.0f || n.p[0] == 1.0f))
+					return bad("scalar image texture: interpolation is 0 (closest) or 1 (bilinear)");
+				for (int k = 1; k <= 2; ++k)
+					if (!(n.p[k] == 0.0f || n.p[k] == 1.0f || n.p[k] == 2.0f || n.p[k] == 3.0f))
+						return bad("scalar image texture: wrap is 0 (black), 1 (clamp), 2 (periodic) or 3 (mirror)");
+				for (uint64_t k = 0; k < need; ++k)
+					if (!std::isfinite(d->spectral_tables[n.table_offset + k]))
+						return bad("scalar image texture: values must be finite");
+				if (d->spectral_tables[n.table_offset + need - 1] != 0.0f)
+					return bad("scalar image texture: the last value (the black texel) must be 0");
+			} else {
+				const bool unary = scalar_is_unary(n.kind);
+				if (n.lhs >= i || (!unary && n.rhs >= i))
+					return bad((what + ": operands must precede the node").c_str());
+				for (uint32_t op : { n.lhs, unary ? n.lhs : n.rhs }) {
+					const prgpu_spectrum& o = d->spectra[op];
+					if (!scalar_is_kind(o.kind) && o.kind != PRGPU_SPEC_CONST)
+						return bad((what + ": a spectral node cannot stand where a scalar is expected (operands are scalar nodes or CONST)").c_str());
+					if (o.kind == PRGPU_SPEC_CONST && !std::isfinite(o.p[0]))
+						return bad((what + ": constant operands must be finite").c_str());
+				}
+				if (scalar_info[i].need > PRGPU_EXPR_MAX_STACK)
+					return bad((what + ": needs an operand stack of " + std::to_string(scalar_info[i].need) + " entries, more than PRGPU_EXPR_MAX_STACK (" + std::to_string(PRGPU_EXPR_MAX_STACK) + ")").c_str(),
+							   PRGPU_EUNSUPPORTED);
+				if (scalar_info[i].length > PRGPU_EXPR_MAX_PROGRAM)
+					return bad((what + ": its program is longer than PRGPU_EXPR_MAX_PROGRAM (" + std::to_string(PRGPU_EXPR_MAX_PROGRAM) + " words)").c_str(), PRGPU_EUNSUPPORTED);
+			}
+			expr_info.push_back(ExprInfo());
+			continue;
+		}
+		if (spec_is_math(n.kind) || n.kind == PRGPU_SPEC_CHECKER) // (their own checks below refuse an operand that does not precede the node)
+			for (uint32_t op : { n.lhs, (n.kind != PRGPU_SPEC_MUL && n.kind != PRGPU_SPEC_CHECKER && spec_is_unary(n.kind)) ? n.lhs : n.rhs })
+				if (op < i && scalar_is_kind(d->spectra[op].kind))
+					return bad(("spectral node " + std::to_string(i) + ": a scalar node cannot stand where a spectrum is expected").c_str(), PRGPU_EUNSUPPORTED);
 		if (n.kind > PRGPU_SPEC_IMAGE) { // the expression nodes (MUL is checked below, as before)
 			const std::string what = "spectral expression node " + std::to_string(i);
 			if (d->n_spectra > 0x00FFFFFFu)
@@ -1196,12 +1244,34 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 		}
 		if (m.kind == PRGPU_MAT_OREN_NAYAR && !std::isfinite(m.roughness_x))
 			return bad("oren-nayar roughness must be finite");
+		if (m.flags & PRGPU_MATF_NODE_MASK) { // scalar parameters bound to scalar nodes: the field holds the node's index
+			const std::string what = "material " + std::to_string(i);
+			for (int slot = 0; slot < SCALAR_SLOTS; ++slot) {
+				if (!(m.flags & scalar_slot_bit(slot)))
+					continue;
+				if (m.kind == PRGPU_MAT_BLEND)
+					return bad((what + ": a scalar node on a blend's factor is not supported (the tree is flattened on the host)").c_str(), PRGPU_EUNSUPPORTED);
+				if (!scalar_slot_of_kind(m.kind, slot))
+					return bad((what + ": a PRGPU_MATF_NODE_* bit on a field its kind does not read").c_str());
+				const uint32_t node = scalar_slot_node(scalar_slot_field(m, slot), d->n_spectra);
+				if (node == PRGPU_INVALID_ID)
+					return bad((what + ": a bound scalar parameter must hold the index of a node of the array").c_str());
+				if (!scalar_is_kind(d->spectra[node].kind))
+					return bad((what + ": a bound scalar parameter must name a scalar node (a spectral node cannot stand where a scalar is expected)").c_str());
+			}
+		}
 		const bool conductor = m.kind == PRGPU_MAT_CONDUCTOR || m.kind == PRGPU_MAT_ROUGH_CONDUCTOR;
 		const bool glass	 = m.kind == PRGPU_MAT_DIELECTRIC || m.kind == PRGPU_MAT_ROUGH_DIELECTRIC;
 		if (conductor && (m.ior >= d->n_spectra || m.k >= d->n_spectra))
 			return bad("conductor eta / k spectrum out of range");
 		if (m.albedo >= d->n_spectra)
 			return bad("material albedo index out of range");
+		if (!mat_is_combinator(m.kind)) { // (a combinator's fields name materials; its albedo is not read)
+			auto scalar_at = [&](uint32_t id) { return id != PRGPU_INVALID_ID && id < d->n_spectra && scalar_is_kind(d->spectra[id].kind); };
+			const bool principled = m.kind == PRGPU_MAT_PRINCIPLED;
+			if (scalar_at(m.albedo) || ((conductor || glass || principled) && scalar_at(m.ior)) || (conductor && scalar_at(m.k)) || (glass && scalar_at(m.transmission)))
+				return bad(("material " + std::to_string(i) + ": a scalar node cannot stand where a spectrum is expected").c_str(), PRGPU_EUNSUPPORTED);
+		}
 		if (glass && (m.ior >= d->n_spectra || (m.transmission != PRGPU_INVALID_ID && m.transmission >= d->n_spectra)))
 			return bad("dielectric index / transmission spectrum out of range");
 		if (m.kind == PRGPU_MAT_PRINCIPLED) {
@@ -1210,7 +1280,7 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 			for (int k = 0; k < PRGPU_PRINCIPLED_COUNT; ++k)
 				if (!std::isfinite(m.principled[k]))
 					return bad("principled parameters must be finite");
-			if (!std::isfinite(m.roughness_x) || !(m.principled[PRGPU_PRINCIPLED_ANISOTROPIC] * 0.9f < 1.0f))
+			if (!std::isfinite(m.roughness_x) || (!(m.flags & (PRGPU_MATF_NODE_PRINCIPLED << PRGPU_PRINCIPLED_ANISOTROPIC)) && !(m.principled[PRGPU_PRINCIPLED_ANISOTROPIC] * 0.9f < 1.0f)))
 				return bad("principled roughness must be finite and anisotropic < 1/0.9");
 		}
 		if (m.kind == PRGPU_MAT_ROUGH_CONDUCTOR || m.kind == PRGPU_MAT_ROUGH_DIELECTRIC) {
@@ -1233,6 +1303,9 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 				return bad("entity wants texture coordinates but none given");
 			if (E.kind != PRGPU_ENTITY_SPHERE || d->tri_material[E.first_tri] == PRGPU_INVALID_ID)
 				continue;
+			auto scalar_bound =[&](const prgpu_material& mm) { return (mm.flags & PRGPU_MATF_NODE_MASK) != 0u; };
+			if (mix_any_leaf(d->materials, d->tri_material[E.first_tri], scalar_bound))
+				return bad("scalar nodes on sphere entities are not supported (their uv needs atan2 / acos)", PRGPU_EUNSUPPORTED);
 			auto textured_material =[&](const prgpu_material& mm) { return textured(mm.albedo) || textured(mm.ior) || textured(mm.k) || textured(mm.transmission); };
 			if (mix_any_leaf(d->materials, d->tri_material[E.first_tri], textured_material)) // (a blend / add: its leaves are what the vertex evaluates)
 				return bad("textured materials on sphere entities are not supported (their uv needs atan2 / acos)", PRGPU_EUNSUPPORTED);
@@ -1283,6 +1356,8 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 		}
 		if (l.radiance >= d->n_spectra || (l.background != PRGPU_INVALID_ID && l.background >= d->n_spectra))
 			return bad("infinite light spectrum index out of range");
+		if (scalar_is_kind(d->spectra[l.radiance].kind) || (l.background != PRGPU_INVALID_ID && scalar_is_kind(d->spectra[l.background].kind)))
+			return bad("infinite light: a scalar node cannot stand where a spectrum is expected", PRGPU_EUNSUPPORTED);
 		if (l.kind == PRGPU_LIGHT_ENVIRONMENT && (l.flags & PRGPU_ENVF_TEXTURED)) {
 			if (l.azimuth_count == 0 || l.elevation_count == 0 || l.azimuth_count > 16384 || l.elevation_count > 16384)
 				return bad("textured environment light: image size must be 1..16384 per axis");
@@ -1311,6 +1386,8 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 			return bad("only diffuse emissions are implemented", PRGPU_EUNSUPPORTED);
 		if (d->emissions[i].radiance >= d->n_spectra)
 			return bad("emission radiance index out of range");
+		if (scalar_is_kind(d->spectra[d->emissions[i].radiance].kind))
+			return bad("emission: a scalar node cannot stand where a spectrum is expected", PRGPU_EUNSUPPORTED);
 		{
 			const prgpu_spectrum& r = d->spectra[d->emissions[i].radiance];
 			if (r.kind == PRGPU_SPEC_SELLMEIER || expr_info[d->emissions[i].radiance].sellmeier) // (alone, or anywhere inside a product or an expression)
@@ -1369,10 +1446,42 @@ bool compile_expressions(const prgpu_scene_desc* d, std::vector<prgpu_spectrum>&
 	// A node that is no root runs no program, whatever the caller left in fields its kind does not use -- in EVERY scene: the top row's
 	// kernels look at table_count of a MUL whether or not the scene has a root (a scene gets there for a disk or a light path expression too).
 	for (uint32_t i = 0; i < d->n_spectra; ++i)
-		if (!root[i] && (spectra[i].kind == PRGPU_SPEC_MUL || spectra[i].kind > PRGPU_SPEC_IMAGE)) {
+		if (!root[i] && (spectra[i].kind == PRGPU_SPEC_MUL || (spectra[i].kind > PRGPU_SPEC_IMAGE && spectra[i].kind <= PRGPU_SPEC_PEAK))) { // (a scalar node is compile_scalar_nodes')
 			spectra[i].table_offset = spectra[i].table_count = 0;
 			spectra[i].wl_start = spectra[i].wl_end = 0.0f;
 		}
+	return any;
+}
+
+bool compile_scalar_nodes(const prgpu_scene_desc* d, std::vector<prgpu_spectrum>& spectra, std::vector<uint32_t>& programs)
+{
+	std::vector<ScalarInfo> info;
+	info.reserve(d->n_spectra);
+	for (uint32_t i = 0; i < d->n_spectra; ++i)
+		info.push_back(scalar_info_of(d->spectra[i], info));
+	std::vector<uint8_t> root(d->n_spectra, 0);
+	bool any = false;
+	for (uint32_t i = 0; i < d->n_materials; ++i) {
+		const prgpu_material& m = d->materials[i];
+		for (int slot = 0; slot < SCALAR_SLOTS; ++slot)
+			if (m.flags & scalar_slot_bit(slot)) {
+				any = true;
+				root[scalar_slot_node(scalar_slot_field(m, slot), d->n_spectra)] = 1; // (validated: a scalar node of the array)
+			}
+	}
+	// an operator's record does not use the table fields: a bound root's copy names its program there, every other one's has them zeroed
+	for (uint32_t i = 0; i < d->n_spectra; ++i) {
+		if (!scalar_is_op(spectra[i].kind))
+			continue;
+		spectra[i].table_offset = spectra[i].table_count = 0;
+		spectra[i].wl_start = spectra[i].wl_end = 0.0f;
+		if (!root[i])
+			continue;
+		const size_t first = programs.size();
+		scalar_emit(d->spectra, info, i, programs);
+		spectra[i].table_offset = uint32_t(d->n_spectral_table_values + first);
+		spectra[i].table_count	= uint32_t(programs.size() - first);
+	}
 	return any;
 }
 

@@ -52,6 +52,11 @@ int build_tables(const prgpu_scene_desc* d, HostTables& t, std::string& err);
 // copy has those fields (which its kind does not use, and a caller may have left anything in) zeroed: the device takes a non-zero
 // table_count there for a program.  Returns whether the scene has a root; `spectra` is what the device gets either way.
 bool compile_expressions(const prgpu_scene_desc* d, std::vector<prgpu_spectrum>& spectra, std::vector<uint32_t>& programs);
+// Scalar nodes (include/prgpu.h; scalar_node.h), after compile_expressions on the same two arrays: the postfix program of every scalar
+// OPERATOR a material's PRGPU_MATF_NODE_* bit binds is appended to `programs`, and the operator's copy names it the way an expression
+// root's does (table_count words at word table_offset); every other operator's copy has those fields zeroed.  A bound SCALAR_IMAGE needs no
+// program (its table fields are its texels').  Returns whether a material binds a node.
+bool compile_scalar_nodes(const prgpu_scene_desc* d, std::vector<prgpu_spectrum>& spectra, std::vector<uint32_t>& programs);
 // Morton-ordered list of the owned pixels (StreamPipeline.cpp:83-133 walks each tile in Morton order)
 void owned_pixels_morton(uint32_t W, uint32_t H, const prgpu_tile* tiles, uint32_t n_tiles, std::vector<uint32_t>& pixels);
 

@@ -95,7 +95,7 @@ inline ExprInfo expr_info_of(const prgpu_spectrum& n, const std::vector<ExprInfo
 	ExprInfo r;
 	r.sellmeier	 = n.kind == PRGPU_SPEC_SELLMEIER;
 	r.varying	 = r.sellmeier || n.kind == PRGPU_SPEC_BLACKBODY || n.kind == PRGPU_SPEC_PEAK;
-	r.expression = n.kind > PRGPU_SPEC_IMAGE;
+	r.expression = n.kind > PRGPU_SPEC_IMAGE && n.kind <= PRGPU_SPEC_PEAK; // (the scalar kinds beyond are no spectra: scalar_node.h)
 	if (!spec_is_math(n.kind))
 		return r;
 	const bool unary = spec_is_unary(n.kind);

@@ -459,8 +459,10 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 	std::vector<prgpu_spectrum> dev_spectra;
 	std::vector<uint32_t> programs;
 	const bool has_expr				 = prgpu_host::compile_expressions(d, dev_spectra, programs);
+	// scalar nodes: the programs of the bound operators follow the expression roots' (setup.h, compile_scalar_nodes)
+	const bool has_scalar			 = prgpu_host::compile_scalar_nodes(d, dev_spectra, programs);
 	const prgpu_spectrum* spectra_up = dev_spectra.data();
-	const uint64_t table_words = uint64_t(d->n_spectral_table_values) + (has_expr ? programs.size() : 0u); // the rows of the blend / add materials follow
+	const uint64_t table_words = uint64_t(d->n_spectral_table_values) + programs.size(); // the rows of the blend / add materials follow
 	std::vector<uint32_t> mix_rows;
 	{
 		uint64_t rows = 0;
@@ -491,11 +493,11 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 	}
 	UP(sc.emissions, d->emissions, d->n_emissions);
 	UP(sc.spectra, spectra_up, d->n_spectra);
-	if (has_expr || !mix_rows.empty()) {
+	if (!programs.empty() || !mix_rows.empty()) {
 		std::vector<float> tables(size_t(table_words) + mix_rows.size());
 		if (d->n_spectral_table_values)
 			std::memcpy(tables.data(), d->spectral_tables, size_t(d->n_spectral_table_values) * sizeof(float));
-		if (has_expr)
+		if (!programs.empty())
 			std::memcpy(tables.data() + d->n_spectral_table_values, programs.data(), programs.size() * sizeof(uint32_t));
 		if (!mix_rows.empty())
 			std::memcpy(tables.data() + table_words, mix_rows.data(), mix_rows.size() * sizeof(uint32_t));
@@ -587,6 +589,8 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 			sc.features |= prd::FEAT_TEXTURES | prd::FEAT_IMAGES;
 	if (has_expr) // the evaluator lives in the top variant only
 		sc.features |= prd::FEAT_EXPR;
+	if (has_scalar) // a material binds a scalar node: scalar_resolve lives in the top variant only
+		sc.features |= prd::FEAT_SCALAR_NODES;
 	for (uint32_t e = 0; e < d->n_entities; ++e)
 		if (d->entities[e].has_uvs && d->uvs && d->entities[e].kind == PRGPU_ENTITY_MESH)
 			sc.features |= prd::FEAT_TEXTURES; // UV-derived tangent frames need the full variant
@@ -607,7 +611,7 @@ int create_impl(const prgpu_scene_desc* d, int device, prgpu_scene* s)
 		else if (d->entities[e].kind == PRGPU_ENTITY_DISK)
 			sc.features |= prd::FEAT_DISKS;
 	// measurement aid: run a scene with a larger kernel variant than it needs (same results; LPE and quadrics need data the scene does not have)
-	sc.features |= read_knobs().force_features & prd::FEAT_ALL & ~(prd::FEAT_LPE | prd::FEAT_QUADRICS | prd::FEAT_DISKS | prd::FEAT_IMAGES | prd::FEAT_MIX_MATERIALS | prd::FEAT_EXPR);
+	sc.features |= read_knobs().force_features & prd::FEAT_ALL & ~(prd::FEAT_LPE | prd::FEAT_QUADRICS | prd::FEAT_DISKS | prd::FEAT_IMAGES | prd::FEAT_MIX_MATERIALS | prd::FEAT_EXPR | prd::FEAT_SCALAR_NODES);
 	sc.scene_radius	 = t.scene_radius;
 	sc.wl_cdf_size	 = (uint32_t)t.wl_cdf.size();
 	sc.wl_u_offset	 = t.wl_u_offset;

@@ -7,7 +7,7 @@
 //
 //   prc_san <file.prc> ...        load each file, walk the description it yields, free it; one status line per file on stdout
 //   prc_san -                     the same for the paths read from stdin (one per line): tools/fuzz_loader.py feeds it thousands of mutants
-//   prc_san --image <file> ... | -   the image reader alone on each file (prgpu_image_load: the size query, then the pixels, all of them read);
+//   prc_san --image <file> ... | -   the image reader alone on each file (prgpu_image_load, then prgpu_image_load_scalar: the size query, then the pixels, all of them read);
 //                                 tools/fuzz_image.py feeds it mutants of its own PNG and PFM seeds
 // Exit code 0 unless a sanitizer aborts the process (ASan / UBSan run with halt_on_error, see the Makefile).
 #include <cstdint>
@@ -102,7 +102,17 @@ static void one_image(const std::string& path)
 		for (float v : rgb)
 			sum += v;
 	}
-	std::printf("%d %u %u %u %d %.9g | %s\n", rc, w, h, ch, lin, sum, path.c_str());
+	// the scalar mode of the same file (prgpu_image_load_scalar: the first channel, not linearised), on the same status line
+	uint32_t sw = 0, sh = 0, sch = 0;
+	int src		= prgpu_image_load_scalar(path.c_str(), &sw, &sh, &sch, nullptr);
+	double ssum = 0.0;
+	if (src == PRGPU_OK) {
+		std::vector<float> values(size_t(sw) * sh);
+		src = prgpu_image_load_scalar(path.c_str(), &sw, &sh, &sch, values.data());
+		for (float v : values)
+			ssum += v;
+	}
+	std::printf("%d %u %u %u %d %.9g scalar %d %.9g | %s\n", rc, w, h, ch, lin, sum, src, ssum, path.c_str());
 }
 
 int main(int argc, char** argv)

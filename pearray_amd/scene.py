@@ -44,11 +44,69 @@ def load_image(path):
     return rgb, ch.value, bool(lin.value)
 
 
+def load_scalar_image(path):
+    """An image file as a `(texture :type 'scalar' ...)` block reads it (prgpu_image_load_scalar): (float32 [H, W] of the file's first
+    channel, rows top-down, not linearised; channels in the file)."""
+    lib = abi.load()
+    w, h, ch = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    args = (os.fsencode(path), C.byref(w), C.byref(h), C.byref(ch))
+    abi.check(lib.prgpu_image_load_scalar(*args, None))
+    values = np.zeros((h.value, w.value), np.float32)
+    abi.check(lib.prgpu_image_load_scalar(*args, values.ctypes.data_as(C.POINTER(C.c_float))))
+    return values, ch.value
+
+
+class ScalarNode:
+    """Handle of a scalar node of a SceneBuilder (scalar_image, scalar_op): what the rough, principled and oren_nayar builders take where
+    they take a number.  `id` is the node's index in the builder's node array."""
+    __slots__ = ("id",)
+
+    def __init__(self, node_id):
+        self.id = int(node_id)
+
+    def __repr__(self):
+        return "ScalarNode(%d)" % self.id
+
+
+def _scalar_fold(name, a, b):
+    """ScalarMathNode.cpp over constants, in float32 (what the .prc loader folds with the std:: float overloads)."""
+    f32 = np.float32
+    a, b = f32(a), f32(b)
+    with np.errstate(all="ignore"):
+        unary = {"sin": np.sin, "cos": np.cos, "tan": np.tan, "asin": np.arcsin, "acos": np.arccos, "atan": np.arctan, "sinh": np.sinh,
+                 "cosh": np.cosh, "tanh": np.tanh, "asinh": np.arcsinh, "acosh": np.arccosh, "atanh": np.arctanh, "exp": np.exp, "log": np.log,
+                 "abs": np.abs, "sqrt": np.sqrt, "cbrt": np.cbrt, "ceil": np.ceil, "floor": np.floor}
+        if name in unary:
+            return f32(unary[name](a))
+        if name in ("neg", "negate"):
+            return f32(-a)
+        if name == "round":   # std::round: halves away from zero
+            return f32(math.copysign(math.floor(abs(float(a)) + 0.5), float(a))) if np.isfinite(a) else a
+        if name == "add":
+            return f32(a + b)
+        if name in ("sub", "subtract"):
+            return f32(a - b)
+        if name in ("mul", "multiply"):
+            return f32(a * b)
+        if name in ("div", "divide"):
+            return f32(a / b)
+        if name == "atan2":
+            return f32(np.arctan2(a, b))
+        if name == "max":     # std::max(a, b) = a < b ? b : a
+            return b if a < b else a
+        if name == "min":     # std::min(a, b) = b < a ? b : a
+            return b if b < a else a
+        if name == "pow":
+            return f32(np.power(a, b))
+    raise KeyError(name)
+
+
 class SceneBuilder:
     def __init__(self, width, height):
         self.settings = abi.default_settings(width, height)
         self.camera = abi.Camera()
         self.spectra, self.tables = [], []
+        self._scalar_info = {}   # scalar operator node -> (operand stack, program length) of its tree
         self.materials, self.emissions, self.entities, self.lights = [], [], [], []
         self._pos, self._nrm, self._idx, self._trimat = [], [], [], []
         self._n_vertices = 0
@@ -184,6 +242,57 @@ class SceneBuilder:
         return self._add_spec(kind=abi.SPEC_IMAGE, lhs=w, rhs=h, table_offset=off, table_count=4 * (h * w + 1),
                               p=[float(interp), float(self.IMAGE_WRAPS[ws.lower()]), float(self.IMAGE_WRAPS[wt.lower()])])
 
+    # ---- scalar nodes (include/prgpu.h, PRGPU_SPEC_SCALAR_*) ------------------------------
+    def scalar_image(self, array2d, interpolation="closest", wrap="black"):
+        """(texture :type 'scalar' ...), TextureParser.cpp:198-202 / ScalarImageNode: `array2d` is a float image [H, W], rows top-down
+        (what load_scalar_image returns: the file's first channel as it is); `interpolation` and `wrap` as image_texture takes them.
+        Returns the ScalarNode of a PRGPU_SPEC_SCALAR_IMAGE node: W*H + 1 single floats, the last one 0 (the black texel)."""
+        values = np.asarray(array2d, dtype=np.float32)
+        assert values.ndim == 2 and 1 <= values.shape[0] <= 4096 and 1 <= values.shape[1] <= 4096 and np.isfinite(values).all()
+        interp = {"closest": 0, "bi": 1, "bilinear": 1}[interpolation.lower()]
+        ws, wt = (wrap, wrap) if isinstance(wrap, str) else wrap
+        h, w = values.shape
+        off = len(self.tables)
+        self.tables.extend(values.reshape(-1).tolist() + [0.0])
+        return ScalarNode(self._add_spec(kind=abi.SPEC_SCALAR_IMAGE, lhs=w, rhs=h, table_offset=off, table_count=h * w + 1,
+                                         p=[float(interp), float(self.IMAGE_WRAPS[ws.lower()]), float(self.IMAGE_WRAPS[wt.lower()])]))
+
+    def scalar_op(self, name, *operands):
+        """A scalar math node by the reference's name (ScalarMathNode.cpp:148-217; _cabi.SCALAR_OPS): ("add", a, b) and the other binary
+        ones, ("neg", a) and the other unary ones.  An operand is a number or a ScalarNode; a missing one is 0, as the reference's default.
+        Over numbers alone the result is the number (float32 arithmetic), as the .prc loader folds it -- every name; with a ScalarNode
+        below it the result is the ScalarNode of the operator's record, for the names the device evaluates."""
+        name = name.lower()
+        kind, arity = abi.SCALAR_OPS[name]
+        ops = list(operands[:arity]) + [0.0] * (arity - len(operands))
+        if not any(isinstance(o, ScalarNode) for o in ops):
+            return float(_scalar_fold(name, ops[0], ops[1] if arity == 2 else 0.0))
+        if kind is None:
+            raise ValueError("scalar_op: a dynamic '%s' (over a scalar texture) is not supported; the device evaluates %s"
+                             % (name, " ".join(sorted(n for n, (k, _) in abi.SCALAR_OPS.items() if k is not None))))
+        ids = [o.id if isinstance(o, ScalarNode) else self.spectrum_const(float(np.float32(o))) for o in ops]
+        info = [self._scalar_info.get(i, (1, 1)) for i in ids]
+        if arity == 1:
+            need, length = info[0][0], info[0][1] + 1
+        else:
+            need = info[0][0] + 1 if info[0][0] == info[1][0] else max(info[0][0], info[1][0])
+            length = info[0][1] + info[1][1] + 1
+        if need > abi.EXPR_MAX_STACK:
+            raise ValueError("scalar_op: the expression needs an operand stack of %d entries, more than PRGPU_EXPR_MAX_STACK (%d)" % (need, abi.EXPR_MAX_STACK))
+        if length > abi.EXPR_MAX_PROGRAM:
+            raise ValueError("scalar_op: the expression's program is longer than PRGPU_EXPR_MAX_PROGRAM (%d words)" % abi.EXPR_MAX_PROGRAM)
+        node = self._add_spec(kind=kind, lhs=ids[0], rhs=ids[1] if arity == 2 else abi.INVALID_ID)
+        self._scalar_info[node] = (need, length)
+        return ScalarNode(node)
+
+    @staticmethod
+    def _scalar_field(value, bit):
+        """(float field, flag bits) of a scalar parameter: a number as it is, a ScalarNode as its index under the field's MATF_NODE_* bit"""
+        if isinstance(value, ScalarNode):
+            assert value.id < (1 << 24)
+            return float(value.id), bit
+        return float(value), 0
+
     # ---- materials / emissions ---------------------------------------------------------------------
     def lambert(self, albedo, two_sided=True):
         m = abi.Material(abi.MAT_LAMBERT, albedo, 1 if two_sided else 0, 0, 0, 0, 0)
@@ -232,8 +341,12 @@ class SceneBuilder:
         return len(self.materials) - 1
 
     def _rough(self, roughness, roughness_y, vndf):
-        rx = float(roughness)
-        ry, flags = (rx, 0) if roughness_y is None else (float(roughness_y), abi.MATF_ANISOTROPIC)
+        """(roughness_x, roughness_y, flags) of a rough kind; either roughness is a number or a ScalarNode"""
+        rx, flags = self._scalar_field(roughness, abi.MATF_NODE_ROUGHNESS_X)
+        ry = rx
+        if roughness_y is not None:
+            ry, bit = self._scalar_field(roughness_y, abi.MATF_NODE_ROUGHNESS_Y)
+            flags |= bit | abi.MATF_ANISOTROPIC
         return rx, ry, flags | (0 if vndf else abi.MATF_NO_VNDF)
 
     def rough_conductor(self, roughness, eta=None, k=None, specularity=None, roughness_y=None, vndf=True):
@@ -263,15 +376,18 @@ class SceneBuilder:
         if unknown:
             raise TypeError("unknown principled parameters: %s" % sorted(unknown))
         flags = (0 if vndf else abi.MATF_NO_VNDF) | (abi.MATF_HAS_TRANSMISSION if ("diffuse_transmission" in params or "specular_transmission" in params) else 0)
-        m = abi.Material(abi.MAT_PRINCIPLED, base, 0, ior, abi.INVALID_ID, 1 if thin else 0, 0, flags, float(roughness), float(roughness))
+        rx, bit = self._scalar_field(roughness, abi.MATF_NODE_ROUGHNESS_X)   # (roughness and each scalar: a number or a ScalarNode)
+        m = abi.Material(abi.MAT_PRINCIPLED, base, 0, ior, abi.INVALID_ID, 1 if thin else 0, 0, flags | bit, rx, rx)
         for i, name in enumerate(abi.PRINCIPLED_PARAMS):
-            m.principled[i] = float(params.get(name, 0.0))
+            m.principled[i], bit = self._scalar_field(params.get(name, 0.0), abi.MATF_NODE_PRINCIPLED << i)
+            m.flags |= bit
         self.materials.append(m)
         return len(self.materials) - 1
 
     def oren_nayar(self, albedo, roughness=0.5):
         """(material :type 'orennayar'|'oren'|'rough'), orennayar.cpp:99-111: one sided, no `two_sided`"""
-        self.materials.append(abi.Material(abi.MAT_OREN_NAYAR, albedo, 0, 0, 0, 0, 0, 0, float(roughness), 0.0))
+        rx, flags = self._scalar_field(roughness, abi.MATF_NODE_ROUGHNESS_X)   # (a number or a ScalarNode)
+        self.materials.append(abi.Material(abi.MAT_OREN_NAYAR, albedo, 0, 0, 0, 0, 0, flags, rx, 0.0))
         return len(self.materials) - 1
 
     def null(self):
