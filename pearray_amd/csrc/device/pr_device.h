@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../../include/prgpu.h"
+#include "node_math.h" // equidistant_lookup, upsample and the rest of the nodes' per-value arithmetic (shared with the host)
 
 // The rough / principled closures: out of line (one shared copy, small kernels) or inlined into the shading body that uses them
 // (PR_INLINE_CLOSURES=1: the compiler then shares the wavelength-independent terms of the four per-wavelength evaluations).
@@ -699,14 +700,6 @@ __device__ __forceinline__ float distribution2d_pdf(const float* d, uint32_t w, 
 	return pdf0 * pdf1;
 }
 
-// EquidistantSpectrum.inl:34-41
-__device__ __forceinline__ float equidistant_lookup(const float* data, int count, float start, float delta, float wavelength)
-{
-	const float af	= fmaxf(0.0f, (wavelength - start) / delta);
-	const int index = (int)fminf(float(count - 2), af);
-	const float t	= fminf(float(count - 1), af) - index;
-	return data[index] * (1 - t) + data[index + 1] * t;
-}
 // CIE.h:41-62
 __device__ __forceinline__ void cie_eval(const float* cie, float wl, float xyz[3])
 {
@@ -718,13 +711,6 @@ __device__ __forceinline__ void cie_eval(const float* cie, float wl, float xyz[3
 		xyz[c]		   = (d[index] * (1 - t) + d[index + 1] * t) / CIE_Y_NORM * CIE_RANGE;
 	}
 }
-// SpectralUpsampler.h:45-49
-__device__ __forceinline__ float upsample(const float* p, float wl)
-{
-	const float x = (p[0] * wl + p[1]) * wl + p[2];
-	return (0.5f * x) * (1.0f / sqrtf(x * x + 1.0f)) + 0.5f;
-}
-
 // MultiJitteredSampler.cpp:21-76
 __device__ __forceinline__ uint32_t mjitt_permute(uint32_t i, uint32_t l, uint32_t p)
 {

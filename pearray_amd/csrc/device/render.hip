@@ -463,25 +463,7 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, uint32_t n_
 }
 
 // ---- shading helpers --------------------------------------------------------------------------------------
-// One texel index of an image texture along an axis of `n` texels, wrapped by `mode` (0 black, 1 clamp, 2 periodic, 3 mirror: period 2n,
-// second half reflected); -1 selects the black texel.  OpenImageIO's wrap functions (texture.h, TextureOpt::Wrap), restated.
-__device__ __forceinline__ int image_wrap(int i, int n, int mode)
-{
-	if (mode == 1)
-		return min(max(i, 0), n - 1);
-	if (mode == 2) {
-		const int r = i % n;
-		return r < 0 ? r + n : r;
-	}
-	if (mode == 3) {
-		int r = i % (2 * n);
-		r	  = r < 0 ? r + 2 * n : r;
-		return r >= n ? 2 * n - 1 - r : r;
-	}
-	return (i < 0 || i >= n) ? -1 : i;
-}
-// a texel coordinate as an integer the wraps can take: floor, held inside +-2^30 (a NaN ends at the lower bound)
-__device__ __forceinline__ int image_floor(float x) { return (int)fminf(fmaxf(floorf(x), -1073741824.0f), 1073741824.0f); }
+// (image_wrap, image_floor: one texel index along an axis, -1 the black texel -- node_math.h)
 __device__ __forceinline__ Blob image_texel_spectrum(const float4 c, const Blob& wl)
 {
 	const float p[3] = { c.x, c.y, c.z };
@@ -532,7 +514,7 @@ __device__ __forceinline__ Blob spectrum_leaf(const DevScene& sc, const prgpu_sp
 			b.v[k] = equidistant_lookup(data, (int)n.table_count, n.wl_start, delta, wl.v[k]);
 		return b;
 	}
-	case PRGPU_SPEC_SELLMEIER: { // Scattering::sellmeier (base/math/Scattering.h:219-242)
+	case PRGPU_SPEC_SELLMEIER: { // sellmeier of node_math.h, restated: through the shared function the lean path kernels compile to other code
 		const uint32_t nc = n.table_count / 2;
 		const float* B	  = sc.tables + n.table_offset;
 		const float* C	  = B + nc;
@@ -563,18 +545,6 @@ __device__ __forceinline__ bool spectrum_varying(const prgpu_spectrum& n)
 {
 	return n.kind == PRGPU_SPEC_SELLMEIER || (EXPR && expr_is_program(n) && n.wl_start != 0.0f);
 }
-// blackbody (core/spectral/Blackbody.h:11-28): Planck's law in double, cast to float, times the node's float peak normalisation
-constexpr double PR_LIGHT_C = 299792458.0, PR_PLANCK_H = 6.62607004081e-34, PR_BOLTZMANN_KB = 1.3806485279e-23; // base/math/SIMathConstants.h:23,37,58
-__device__ __forceinline__ float expr_blackbody(float lambda_nm, float temp_kelvin)
-{
-	const double lambda	 = (double)(lambda_nm * 1e-9f);
-	const double temp	 = (double)temp_kelvin;
-	const double c1		 = 2 * PR_PLANCK_H * PR_LIGHT_C * PR_LIGHT_C;
-	const double c2		 = PR_PLANCK_H * PR_LIGHT_C / PR_BOLTZMANN_KB;
-	const double lambda5 = lambda * (lambda * lambda) * (lambda * lambda);
-	const double f		 = c2 / (lambda * temp);
-	return (float)((c1 / lambda5) / expm1(f));
-}
 // the two leaves only expressions have
 __device__ __forceinline__ Blob expr_leaf(const DevScene& sc, const prgpu_spectrum& n, const Blob& wl)
 {
@@ -584,42 +554,12 @@ __device__ __forceinline__ Blob expr_leaf(const DevScene& sc, const prgpu_spectr
 			b.v[k] = expr_blackbody(wl.v[k], n.p[0]) * n.p[1];
 		return b;
 	}
-	if (n.kind == PRGPU_SPEC_PEAK) { // evalTriangle (TrianglePeakNode.cpp:8-11)
+	if (n.kind == PRGPU_SPEC_PEAK) {
 		for (int k = 0; k < 4; ++k)
-			b.v[k] = fmaxf(0.0f, 1.0f - fabsf(wl.v[k] - n.p[0]) / n.p[1]);
+			b.v[k] = expr_peak(wl.v[k], n.p[0], n.p[1]);
 		return b;
 	}
 	return spectrum_leaf(sc, n, wl);
-}
-// one lane of a unary / binary / parametrised operator (SpectralMathNode.cpp:67-96,128,188-194), in the reference's operand order
-__device__ __forceinline__ float expr_op(uint32_t kind, float a, float b, float p0, float p1)
-{
-	switch (kind) {
-	case PRGPU_SPEC_MUL: return a * b;
-	case PRGPU_SPEC_ADD: return a + b;
-	case PRGPU_SPEC_SUB: return a - b;
-	case PRGPU_SPEC_DIV: return a / b;
-	case PRGPU_SPEC_NEG: return -a;
-	case PRGPU_SPEC_ABS: return fabsf(a);
-	case PRGPU_SPEC_MAX: return fmaxf(a, b);
-	case PRGPU_SPEC_MIN: return fminf(a, b);
-	case PRGPU_SPEC_BURN: return 1 - (1 - a) / (b + 1);
-	case PRGPU_SPEC_SCREEN: return 1 - (1 - a) * (1 - b);
-	case PRGPU_SPEC_DODGE: return a / ((1 - b) + 1);
-	case PRGPU_SPEC_OVERLAY: return a * (a + 2 * b * (1 - a));
-	case PRGPU_SPEC_SOFTLIGHT: {
-		const float r = 1 - (1 - a) * (1 - b);
-		return ((1 - a) * b + r) * a;
-	}
-	case PRGPU_SPEC_HARDLIGHT: {
-		const float k1 = 1 - (1 - 2 * (b - 0.5f)) * (1 - a);
-		const float k2 = 2 * b * a;
-		return b <= 0.5f ? k2 : k1;
-	}
-	case PRGPU_SPEC_BLEND: return a * (1 - p0) + b * p0;
-	case PRGPU_SPEC_BRIGHTNESS_CONTRAST: return fmaxf((1.0f + p1) * a + (p0 - p1 * 0.5f), 0.0f);
-	default: return 0.0f;
-	}
 }
 // The stack machine over four-wavelength blobs.  The operand stack is four NAMED blobs that shift on a push and a pop (s0 is the top): no
 // runtime-indexed array, so nothing goes to scratch.  The scene bounds the depth (PRGPU_EXPR_MAX_STACK = 4) and the program's length.
@@ -634,8 +574,8 @@ static __device__ __attribute__((noinline)) Blob expr_eval(const DevScene& sc, c
 		const uint32_t word		= prog[i];
 		const prgpu_spectrum& n = sc.spectra[word & EXPR_NODE_MASK];
 		const uint32_t kind		= n.kind;
-		if (kind == PRGPU_SPEC_MUL || (kind > PRGPU_SPEC_IMAGE && kind < PRGPU_SPEC_BLACKBODY)) {
-			const bool unary = kind == PRGPU_SPEC_NEG || kind == PRGPU_SPEC_ABS || kind == PRGPU_SPEC_BRIGHTNESS_CONTRAST;
+		if (spec_is_math(kind)) {
+			const bool unary = spec_is_unary(kind);
 			const bool swap	 = (word & EXPR_SWAP) != 0u;
 			const Blob a = unary ? s0 : (swap ? s0 : s1), b = swap ? s1 : s0;
 			Blob r;
@@ -729,30 +669,6 @@ __device__ __forceinline__ float scalar_image_eval(const DevScene& sc, const prg
 	const float v01 = tex[(i0 < 0 || j1 < 0) ? black : j1 * W + i0], v11 = tex[(i1 < 0 || j1 < 0) ? black : j1 * W + i1];
 	return (v00 * (1.0f - fx) + v10 * fx) * (1.0f - fy) + (v01 * (1.0f - fx) + v11 * fx) * fy;
 }
-// one operator of ScalarMathNode.cpp:109-144 that runs on the device, in the reference's operand order (std::max / std::min as they compare)
-__device__ __forceinline__ float scalar_op(uint32_t kind, float a, float b)
-{
-	switch (kind) {
-	case PRGPU_SPEC_SCALAR_ADD: return a + b;
-	case PRGPU_SPEC_SCALAR_SUB: return a - b;
-	case PRGPU_SPEC_SCALAR_MUL: return a * b;
-	case PRGPU_SPEC_SCALAR_DIV: return a / b;
-	case PRGPU_SPEC_SCALAR_NEG: return -a;
-	case PRGPU_SPEC_SCALAR_ABS: return fabsf(a);
-	case PRGPU_SPEC_SCALAR_MAX: return a < b ? b : a;
-	case PRGPU_SPEC_SCALAR_MIN: return b < a ? b : a;
-	case PRGPU_SPEC_SCALAR_SQRT: return sqrtf(a);
-	case PRGPU_SPEC_SCALAR_POW: return powf(a, b);
-	case PRGPU_SPEC_SCALAR_FLOOR: return floorf(a);
-	case PRGPU_SPEC_SCALAR_CEIL: return ceilf(a);
-	case PRGPU_SPEC_SCALAR_ROUND: return roundf(a);
-	case PRGPU_SPEC_SCALAR_EXP: return expf(a);
-	case PRGPU_SPEC_SCALAR_LOG: return logf(a);
-	case PRGPU_SPEC_SCALAR_SIN: return sinf(a);
-	case PRGPU_SPEC_SCALAR_COS: return cosf(a);
-	default: return 0.0f;
-	}
-}
 // The stack machine of expr_eval over single floats: a bound operator's record names its postfix program (table_count words at word
 // table_offset of DevScene::tables; host/setup.cpp, compile_scalar_nodes), a word is a node index and EXPR_SWAP.  Four NAMED stack entries
 // that shift on a push and a pop (s0 is the top): no runtime-indexed array.  The scene bounds the depth and the program's length.
@@ -766,7 +682,7 @@ __device__ __forceinline__ float scalar_run(const DevScene& sc, const prgpu_spec
 		const uint32_t word		= prog[i];
 		const prgpu_spectrum& n = sc.spectra[word & EXPR_NODE_MASK];
 		const uint32_t kind		= n.kind;
-		if (kind >= PRGPU_SPEC_SCALAR_ADD) {
+		if (kind >= PRGPU_SPEC_SCALAR_ADD) { // scalar_is_op / scalar_is_unary of node_math.h, restated: through the shared predicates k_shade compiles to other code
 			const bool unary = kind != PRGPU_SPEC_SCALAR_ADD && kind != PRGPU_SPEC_SCALAR_SUB && kind != PRGPU_SPEC_SCALAR_MUL && kind != PRGPU_SPEC_SCALAR_DIV
 							   && kind != PRGPU_SPEC_SCALAR_MAX && kind != PRGPU_SPEC_SCALAR_MIN && kind != PRGPU_SPEC_SCALAR_POW;
 			const bool swap	 = (word & EXPR_SWAP) != 0u;

@@ -217,6 +217,15 @@ struct Loader {
 
 	// ---- spectral expressions ----------------------------------------------------------------------------------
 	std::vector<prgpu_host::ExprInfo> expr_info; // per node of out.spectra (spectral_expr.h): the two bounds of the device evaluator are refused where the node is written
+	// the two bounds of the device evaluators (node_program.h), refused where the node is written; `what` is the family's word for its trees
+	void refuse_beyond_evaluator(const prgpu_host::ProgramExtent& x, const Group& e, const std::string& what)
+	{
+		if (x.need > PRGPU_EXPR_MAX_STACK)
+			fail(PRGPU_EUNSUPPORTED, where(e) + ": the " + what + " needs an operand stack of " + std::to_string(x.need) + " entries, more than the device evaluator's " + std::to_string(PRGPU_EXPR_MAX_STACK)
+										 + " (PRGPU_EXPR_MAX_STACK)");
+		if (x.length > PRGPU_EXPR_MAX_PROGRAM)
+			fail(PRGPU_EUNSUPPORTED, where(e) + ": the " + what + "'s program is longer than the device evaluator's " + std::to_string(PRGPU_EXPR_MAX_PROGRAM) + " words (PRGPU_EXPR_MAX_PROGRAM)");
+	}
 	uint32_t add_spectrum(const prgpu_spectrum& s, const Group* e = nullptr)
 	{
 		if (e && prgpu_host::spec_is_math(s.kind)) { // no uv-dependent node below a math node (the words smul always had)
@@ -232,11 +241,8 @@ struct Loader {
 		out.spectra.push_back(s);
 		expr_info.push_back(prgpu_host::expr_info_of(s, expr_info, out.spectra.data()));
 		const prgpu_host::ExprInfo& info = expr_info.back();
-		if (e && info.expression && info.need > PRGPU_EXPR_MAX_STACK)
-			fail(PRGPU_EUNSUPPORTED, where(*e) + ": the expression needs an operand stack of " + std::to_string(info.need) + " entries, more than the device evaluator's " + std::to_string(PRGPU_EXPR_MAX_STACK)
-										 + " (PRGPU_EXPR_MAX_STACK)");
-		if (e && info.expression && info.length > PRGPU_EXPR_MAX_PROGRAM)
-			fail(PRGPU_EUNSUPPORTED, where(*e) + ": the expression's program is longer than the device evaluator's " + std::to_string(PRGPU_EXPR_MAX_PROGRAM) + " words (PRGPU_EXPR_MAX_PROGRAM)");
+		if (e && info.expression)
+			refuse_beyond_evaluator(info, *e, "expression");
 		return (uint32_t)out.spectra.size() - 1;
 	}
 	// lookupSpectralNode (SceneLoadContext.cpp:201-234) of positional parameter `k` of a math node: default 0, for a missing one too
@@ -598,21 +604,28 @@ struct Loader {
 		const std::string w = v.type == Value::STRING ? lower(v.s) : std::string();
 		return w == "clamp" ? 1 : w == "periodic" ? 2 : w == "mirror" ? 3 : 0;
 	}
-	// the node of an image (height x width x 3 linear RGB, rows top-down): one four-float texel of coefficients per pixel, then the black texel
-	uint32_t spectrum_image(const float* rgb, uint32_t w, uint32_t h, int interpolation, int wrap_s, int wrap_t)
+	// the record of an image node of `kind` whose texels (`stride` floats each, W H of them and the black one) the caller appends to out.tables next
+	prgpu_spectrum image_record(uint32_t kind, uint32_t stride, uint32_t w, uint32_t h, int interpolation, int wrap_s, int wrap_t)
 	{
-		prgpu_spectrum s = blank(PRGPU_SPEC_IMAGE);
+		prgpu_spectrum s = blank(kind);
 		s.lhs			 = w;
 		s.rhs			 = h;
 		s.p[0]			 = (float)interpolation;
 		s.p[1]			 = (float)wrap_s;
 		s.p[2]			 = (float)wrap_t;
-		out.tables.resize((out.tables.size() + 3) / 4 * 4, 0.0f); // a texel is one aligned 16-byte record
 		const uint64_t n = uint64_t(w) * h + 1;
-		if (uint64_t(out.tables.size()) + 4 * n > 0xFFFFFFFFull)
+		if (uint64_t(out.tables.size()) + stride * n > 0xFFFFFFFFull)
 			fail(PRGPU_EUNSUPPORTED, "the scene's image textures exceed the table array");
 		s.table_offset = (uint32_t)out.tables.size();
-		s.table_count  = (uint32_t)(4 * n);
+		s.table_count  = (uint32_t)(stride * n);
+		return s;
+	}
+	// the node of an image (height x width x 3 linear RGB, rows top-down): one four-float texel of coefficients per pixel, then the black texel
+	uint32_t spectrum_image(const float* rgb, uint32_t w, uint32_t h, int interpolation, int wrap_s, int wrap_t)
+	{
+		out.tables.resize((out.tables.size() + 3) / 4 * 4, 0.0f); // a texel is one aligned 16-byte record
+		const prgpu_spectrum s = image_record(PRGPU_SPEC_IMAGE, 4, w, h, interpolation, wrap_s, wrap_t);
+		const uint64_t n	   = uint64_t(w) * h + 1;
 		std::map<std::array<uint32_t, 3>, std::array<float, 3>> memo; // an 8-bit image has few distinct colours
 		const float black[3] = { 0.0f, 0.0f, 0.0f };
 		for (uint64_t i = 0; i < n; ++i) {
@@ -758,17 +771,8 @@ struct Loader {
 	// the node of a scalar image (height x width floats, rows top-down): one float per pixel, then the black texel
 	uint32_t scalar_image(const float* values, uint32_t w, uint32_t h, int interpolation, int wrap_s, int wrap_t)
 	{
-		prgpu_spectrum s = blank(PRGPU_SPEC_SCALAR_IMAGE);
-		s.lhs			 = w;
-		s.rhs			 = h;
-		s.p[0]			 = (float)interpolation;
-		s.p[1]			 = (float)wrap_s;
-		s.p[2]			 = (float)wrap_t;
-		const uint64_t n = uint64_t(w) * h + 1;
-		if (uint64_t(out.tables.size()) + n > 0xFFFFFFFFull)
-			fail(PRGPU_EUNSUPPORTED, "the scene's image textures exceed the table array");
-		s.table_offset = (uint32_t)out.tables.size();
-		s.table_count  = (uint32_t)n;
+		const prgpu_spectrum s = image_record(PRGPU_SPEC_SCALAR_IMAGE, 1, w, h, interpolation, wrap_s, wrap_t);
+		const uint64_t n	   = uint64_t(w) * h + 1;
 		out.tables.insert(out.tables.end(), values, values + (n - 1));
 		out.tables.push_back(0.0f);
 		return add_spectrum(s);
@@ -820,11 +824,7 @@ struct Loader {
 		r.id   = add_spectrum(s);
 		scalar_info.resize(r.id);
 		scalar_info.push_back(prgpu_host::scalar_info_of(s, scalar_info));
-		if (scalar_info[r.id].need > PRGPU_EXPR_MAX_STACK)
-			fail(PRGPU_EUNSUPPORTED, where(e) + ": the scalar expression needs an operand stack of " + std::to_string(scalar_info[r.id].need) + " entries, more than the device evaluator's "
-										 + std::to_string(PRGPU_EXPR_MAX_STACK) + " (PRGPU_EXPR_MAX_STACK)");
-		if (scalar_info[r.id].length > PRGPU_EXPR_MAX_PROGRAM)
-			fail(PRGPU_EUNSUPPORTED, where(e) + ": the scalar expression's program is longer than the device evaluator's " + std::to_string(PRGPU_EXPR_MAX_PROGRAM) + " words (PRGPU_EXPR_MAX_PROGRAM)");
+		refuse_beyond_evaluator(scalar_info[r.id], e, "scalar expression");
 		return r;
 	}
 	// A material's scalar parameter `key` into float field `slot` of `m` (scalar_node.h): a number; an inline group; or a string that names a
@@ -866,37 +866,7 @@ struct Loader {
 	// arithmetic of spectrum_leaf / spectrum_eval on the device
 	float eval_spectrum_at(uint32_t id, float wl) const
 	{
-		auto leaf = [&](const prgpu_spectrum& n) -> float {
-			switch (n.kind) {
-			case PRGPU_SPEC_CONST: return n.p[0];
-			case PRGPU_SPEC_PARAMETRIC:
-			case PRGPU_SPEC_PARAMETRIC_SCALED: {
-				const float x = (n.p[0] * wl + n.p[1]) * wl + n.p[2];
-				const float v = (0.5f * x) * (1.0f / std::sqrt(x * x + 1.0f)) + 0.5f;
-				return n.kind == PRGPU_SPEC_PARAMETRIC ? v : v * n.p[3];
-			}
-			case PRGPU_SPEC_TABLE: {
-				const float delta = (n.wl_end - n.wl_start) / (n.table_count - 1);
-				const float af	  = std::max(0.0f, (wl - n.wl_start) / delta);
-				const int index	  = (int)std::min<float>(float(n.table_count - 2), af);
-				const float t	  = std::min<float>(float(n.table_count - 1), af) - index;
-				const float* data = out.tables.data() + n.table_offset;
-				return data[index] * (1 - t) + data[index + 1] * t;
-			}
-			case PRGPU_SPEC_SELLMEIER: { // Scattering::sellmeier (base/math/Scattering.h:219-242), as spectrum_leaf on the device
-				const uint32_t nc = n.table_count / 2;
-				const float* B	  = out.tables.data() + n.table_offset;
-				const float* C	  = B + nc;
-				const float lq	  = wl / 1000;
-				const float lq2	  = lq * lq;
-				float value		  = 1.0f;
-				for (uint32_t i = 0; i < nc; ++i)
-					value += B[i] * lq2 / (lq2 - C[i]);
-				return std::sqrt(value);
-			}
-			default: return 0.0f;
-			}
-		};
+		auto leaf = [&](const prgpu_spectrum& n) { return prgpu_host::spectrum_leaf_at(n, out.tables.data(), wl); };
 		// a checkerboard is asked at UV (0, 0), where the sky model's ShadingContext stands (SkyModel.cpp:30-34): the even cell, i.e. the
 		// operand resolve_texture (render.hip) picks there
 		for (int guard = 0; id < out.spectra.size() && out.spectra[id].kind == PRGPU_SPEC_CHECKER && guard < 64; ++guard)

@@ -1,9 +1,12 @@
 // scalar_node.h -- the host's half of the scalar nodes (include/prgpu.h, PRGPU_SPEC_SCALAR_IMAGE .. PRGPU_SPEC_SCALAR_COS and the
 // PRGPU_MATF_NODE_* bits): what the .prc loader, validate_desc and the compile to postfix programs share.
-// Header only, like spectral_expr.h: the loader is also built without setup.cpp (the sanitizer driver).  The arithmetic restates
-// ScalarMathNode.cpp (fp32, the std:: float overloads); scalar_op of device/render.hip restates the device's share of it.
+// Header only, like spectral_expr.h: the loader is also built without setup.cpp (the sanitizer driver).  The operators that have a device
+// kind are the device's own text (device/node_math.h, scalar_op); the names that only fold on the host restate ScalarMathNode.cpp here
+// (fp32, the std:: float overloads).  The program format is node_program.h's.
 #pragma once
 #include "../../../include/prgpu.h"
+#include "../device/node_math.h"
+#include "node_program.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -12,13 +15,10 @@
 #include <vector>
 
 namespace prgpu_host {
-inline bool scalar_is_op(uint32_t kind) { return kind >= PRGPU_SPEC_SCALAR_ADD && kind <= PRGPU_SPEC_SCALAR_COS; }
+using prd::scalar_is_op;
+using prd::scalar_is_unary;
 inline bool scalar_is_kind(uint32_t kind) { return kind == PRGPU_SPEC_SCALAR_IMAGE || scalar_is_op(kind); }
-inline bool scalar_is_unary(uint32_t kind)
-{
-	return scalar_is_op(kind) && kind != PRGPU_SPEC_SCALAR_ADD && kind != PRGPU_SPEC_SCALAR_SUB && kind != PRGPU_SPEC_SCALAR_MUL && kind != PRGPU_SPEC_SCALAR_DIV
-		   && kind != PRGPU_SPEC_SCALAR_MAX && kind != PRGPU_SPEC_SCALAR_MIN && kind != PRGPU_SPEC_SCALAR_POW;
-}
+constexpr NodeFamily SCALAR_FAMILY = { scalar_is_op, scalar_is_unary };
 
 // The 32 names ScalarMathPlugin registers (ScalarMathNode.cpp:219-228) and `pow`, whose class the file defines (:144) without registering
 // it: accepted here.  `kind` is the device enumerator, or 0 for a name that only folds on the host.
@@ -43,16 +43,13 @@ inline const ScalarOpName* scalar_op_by_name(const std::string& name)
 			return &op;
 	return nullptr;
 }
-// FloatScalarNode::eval of a math node over constants (ScalarMathNode.cpp:109-144), by name: every name folds
+// FloatScalarNode::eval of a math node over constants (ScalarMathNode.cpp:109-144), by name: every name folds -- a name that has a device
+// kind by the device's scalar_op, the others here
 inline float scalar_fold(const std::string& name, float a, float b)
 {
-	if (name == "add") return a + b;
-	if (name == "sub" || name == "subtract") return a - b;
-	if (name == "mul" || name == "multiply") return a * b;
-	if (name == "div" || name == "divide") return a / b;
-	if (name == "neg" || name == "negate") return -a;
-	if (name == "sin") return std::sin(a);
-	if (name == "cos") return std::cos(a);
+	const ScalarOpName* op = scalar_op_by_name(name);
+	if (op && op->kind != 0)
+		return prd::scalar_op(op->kind, a, b);
 	if (name == "tan") return std::tan(a);
 	if (name == "asin") return std::asin(a);
 	if (name == "acos") return std::acos(a);
@@ -63,18 +60,8 @@ inline float scalar_fold(const std::string& name, float a, float b)
 	if (name == "asinh") return std::asinh(a);
 	if (name == "acosh") return std::acosh(a);
 	if (name == "atanh") return std::atanh(a);
-	if (name == "exp") return std::exp(a);
-	if (name == "log") return std::log(a);
-	if (name == "abs") return std::abs(a);
-	if (name == "sqrt") return std::sqrt(a);
 	if (name == "cbrt") return std::cbrt(a);
-	if (name == "ceil") return std::ceil(a);
-	if (name == "floor") return std::floor(a);
-	if (name == "round") return std::round(a);
 	if (name == "atan2") return std::atan2(a, b);
-	if (name == "max") return std::max(a, b);
-	if (name == "min") return std::min(a, b);
-	if (name == "pow") return std::pow(a, b);
 	return 0.0f;
 }
 
@@ -103,49 +90,21 @@ inline uint32_t scalar_slot_node(float field, uint32_t n_spectra)
 	return uint32_t(field);
 }
 
-// operand stack and program length of a scalar node from its operands' (which precede it), as ExprInfo has them for the spectral nodes
-struct ScalarInfo {
-	uint32_t need = 1, length = 1;
+// the extent of a scalar node's program (node_program.h) from its operands' (which precede it), as ExprInfo has it for the spectral nodes
+struct ScalarInfo : ProgramExtent {
 	bool textured = false; // a SCALAR_IMAGE somewhere below
 };
 inline ScalarInfo scalar_info_of(const prgpu_spectrum& n, const std::vector<ScalarInfo>& info)
 {
 	ScalarInfo r;
 	r.textured = n.kind == PRGPU_SPEC_SCALAR_IMAGE;
-	if (!scalar_is_op(n.kind))
+	const ScalarInfo *a, *b;
+	if (!program_operands(SCALAR_FAMILY, n, info, a, b))
 		return r;
-	const bool unary = scalar_is_unary(n.kind);
-	if (n.lhs >= info.size() || (!unary && n.rhs >= info.size())) // (refused by the caller)
-		return r;
-	const ScalarInfo& a = info[n.lhs];
-	if (unary) {
-		r		 = a;
-		r.length = std::min<uint32_t>(a.length + 1u, 1u << 20);
-		return r;
-	}
-	const ScalarInfo& b = info[n.rhs];
-	r.need				= a.need == b.need ? a.need + 1u : std::max(a.need, b.need);
-	r.length			= std::min<uint32_t>(a.length + b.length + 1u, 1u << 20);
-	r.textured			= a.textured || b.textured;
+	static_cast<ProgramExtent&>(r) = program_extent(*a, b);
+	r.textured					   = a->textured || (b && b->textured);
 	return r;
 }
-// postfix program of the scalar tree rooted at `id` (device/render.hip, scalar_run): the words of expr_emit -- a node index, bit 31 when the
-// right operand went first (the one that needs the deeper stack does)
-inline void scalar_emit(const prgpu_spectrum* spectra, const std::vector<ScalarInfo>& info, uint32_t id, std::vector<uint32_t>& out)
-{
-	const prgpu_spectrum& n = spectra[id];
-	if (!scalar_is_op(n.kind)) {
-		out.push_back(id);
-		return;
-	}
-	if (scalar_is_unary(n.kind)) {
-		scalar_emit(spectra, info, n.lhs, out);
-		out.push_back(id);
-		return;
-	}
-	const bool swap = info[n.rhs].need > info[n.lhs].need;
-	scalar_emit(spectra, info, swap ? n.rhs : n.lhs, out);
-	scalar_emit(spectra, info, swap ? n.lhs : n.rhs, out);
-	out.push_back(id | (swap ? 0x80000000u : 0u));
-}
+// postfix program of the scalar tree rooted at `id`, for scalar_run of device/render.hip
+inline void scalar_emit(const prgpu_spectrum* spectra, const std::vector<ScalarInfo>& info, uint32_t id, std::vector<uint32_t>& out) { program_emit(SCALAR_FAMILY, spectra, info, id, out); }
 } // namespace prgpu_host

@@ -113,33 +113,18 @@ uint64_t mcg_pow(uint64_t delta)
 struct V4 {
 	float v[4];
 };
-float lookup_table(const float* data, int count, float start, float delta, float wl)
+// one wavelength of a plain leaf: spectrum_leaf_at (spectral_expr.h), but for SELLMEIER.  This evaluator has always answered 0 for a
+// refractive-index node, which validate_desc does not refuse as an infinite light's radiance (it does as an emission's), where the device's
+// spectrum_leaf answers the index: kept as it is -- the light's power and the wavelength distribution built from it depend on it.
+float eval_leaf_at(const prgpu_scene_desc* d, const prgpu_spectrum& n, float wl)
 {
-	const float af	= std::max(0.0f, (wl - start) / delta);
-	const int index = (int)std::min<float>(float(count - 2), af);
-	const float t	= std::min<float>(float(count - 1), af) - index;
-	return data[index] * (1 - t) + data[index + 1] * t;
-}
-float sigmoid_poly(const float* p, float wl)
-{
-	const float x = (p[0] * wl + p[1]) * wl + p[2];
-	return (0.5f * x) * (1.0f / std::sqrt(x * x + 1.0f)) + 0.5f;
+	if (n.kind == PRGPU_SPEC_SELLMEIER)
+		return 0.0f;
+	return spectrum_leaf_at(n, d->spectral_tables, wl);
 }
 V4 eval_leaf(const prgpu_scene_desc* d, const prgpu_spectrum& n, const V4& wl)
 {
-	V4 r{ { 0, 0, 0, 0 } };
-	for (int k = 0; k < 4; ++k) {
-		switch (n.kind) {
-		case PRGPU_SPEC_CONST: r.v[k] = n.p[0]; break;
-		case PRGPU_SPEC_PARAMETRIC: r.v[k] = sigmoid_poly(n.p, wl.v[k]); break;
-		case PRGPU_SPEC_PARAMETRIC_SCALED: r.v[k] = sigmoid_poly(n.p, wl.v[k]) * n.p[3]; break;
-		case PRGPU_SPEC_TABLE:
-			r.v[k] = lookup_table(d->spectral_tables + n.table_offset, (int)n.table_count, n.wl_start, (n.wl_end - n.wl_start) / (n.table_count - 1), wl.v[k]);
-			break;
-		default: break;
-		}
-	}
-	return r;
+	return V4{ { eval_leaf_at(d, n, wl.v[0]), eval_leaf_at(d, n, wl.v[1]), eval_leaf_at(d, n, wl.v[2]), eval_leaf_at(d, n, wl.v[3]) } };
 }
 V4 eval_spectrum(const prgpu_scene_desc* d, uint32_t id, const V4& wl)
 {
@@ -148,7 +133,7 @@ V4 eval_spectrum(const prgpu_scene_desc* d, uint32_t id, const V4& wl)
 		// an expression: the operators and the two leaves of spectral_expr.h, the statements of expr_eval on the device
 		V4 r;
 		for (int k = 0; k < 4; ++k)
-			r.v[k] = expr_eval_at(d->spectra, d->n_spectra, id, wl.v[k], [&](const prgpu_spectrum& leaf, float w) { return eval_leaf(d, leaf, V4{ { w, w, w, w } }).v[0]; });
+			r.v[k] = expr_eval_at(d->spectra, d->n_spectra, id, wl.v[k], [&](const prgpu_spectrum& leaf, float w) { return eval_leaf_at(d, leaf, w); });
 		return r;
 	}
 	if (n.kind != PRGPU_SPEC_MUL)
@@ -265,7 +250,7 @@ V4 env_image_eval(const prgpu_scene_desc* d, const prgpu_light& l, const V4& wl,
 	const V4 base	   = eval_spectrum(d, l.radiance, wl);
 	V4 r;
 	for (int k = 0; k < 4; ++k)
-		r.v[k] = base.v[k] * sigmoid_poly(c, wl.v[k]);
+		r.v[k] = base.v[k] * prd::upsample(c, wl.v[k]);
 	return r;
 }
 // NodeUtils::average over the 32 x 32 UV grid in Morton order (shader/NodeUtils.cpp:7-47, math/Bits.h morton_2_xy)
@@ -326,7 +311,7 @@ void cie_xyz(float wl, float xyz[3])
 {
 	const float* planes[3] = { PR_CIE2006_X, PR_CIE2006_Y, PR_CIE2006_Z };
 	for (int c = 0; c < 3; ++c)
-		xyz[c] = lookup_table(planes[c], prd::CIE_SAMPLES, prd::CIE_START, prd::CIE_DELTA, wl) / prd::CIE_Y_NORM * prd::CIE_RANGE;
+		xyz[c] = prd::equidistant_lookup(planes[c], prd::CIE_SAMPLES, prd::CIE_START, prd::CIE_DELTA, wl) / prd::CIE_Y_NORM * prd::CIE_RANGE;
 }
 
 void entity_tables(const prgpu_scene_desc* d, HostTables& t)
@@ -1026,6 +1011,158 @@ int check_combinator(const prgpu_material* mats, uint32_t i, std::vector<MixExte
 	err		  = mix_extent_refusal(extent[i], what);
 	return err.empty() ? PRGPU_OK : PRGPU_EUNSUPPORTED;
 }
+// The refusal of a node whose program exceeds one of the device evaluators' two bounds (the operand stack is asked first), "" within them;
+// `what` names the node in its family's words.
+std::string program_refusal(const ProgramExtent& e, const std::string& what)
+{
+	if (e.need > PRGPU_EXPR_MAX_STACK)
+		return what + ": needs an operand stack of " + std::to_string(e.need) + " entries, more than PRGPU_EXPR_MAX_STACK (" + std::to_string(PRGPU_EXPR_MAX_STACK) + ")";
+	if (e.length > PRGPU_EXPR_MAX_PROGRAM)
+		return what + ": its program is longer than PRGPU_EXPR_MAX_PROGRAM (" + std::to_string(PRGPU_EXPR_MAX_PROGRAM) + " words)";
+	return std::string();
+}
+// An image node's record (IMAGE: `stride` 4, a texel is one aligned record of three coefficients and a 0; SCALAR_IMAGE: stride 1): lhs x rhs
+// texels of 1..4096 each way, p[0] the interpolation, p[1] / p[2] the wraps, stride (W H + 1) finite floats in the table array, the black
+// texel last.  Returns the family's message for the first requirement the record misses, or null.
+struct ImageRefusals {
+	const char *size, *extent, *interpolation, *wrap, *finite, *black;
+};
+constexpr ImageRefusals SPECTRUM_IMAGE_REFUSALS = { "image texture: width and height must be 1..4096",
+													"image texture: 4 (W H + 1) floats at a table_offset that is a multiple of 4, inside spectral_tables",
+													"image texture: interpolation is 0 (closest) or 1 (bilinear)",
+													"image texture: wrap is 0 (black), 1 (clamp), 2 (periodic) or 3 (mirror)",
+													"image texture: texel coefficients must be finite",
+													nullptr }; // (the black texel's coefficients are the upsampler's: not 0)
+constexpr ImageRefusals SCALAR_IMAGE_REFUSALS	= { "scalar image texture: width and height must be 1..4096",
+													"scalar image texture: W H + 1 floats inside spectral_tables",
+													"scalar image texture: interpolation is 0 (closest) or 1 (bilinear)",
+													"scalar image texture: wrap is 0 (black), 1 (clamp), 2 (periodic) or 3 (mirror)",
+													"scalar image texture: values must be finite",
+													"scalar image texture: the last value (the black texel) must be 0" };
+const char* image_record_refusal(const prgpu_scene_desc* d, const prgpu_spectrum& n, uint32_t stride, const ImageRefusals& msg)
+{
+	if (n.lhs == 0 || n.rhs == 0 || n.lhs > 4096 || n.rhs > 4096)
+		return msg.size;
+	const uint64_t need = stride * (uint64_t(n.lhs) * n.rhs + 1);
+	if (n.table_offset % stride != 0 || n.table_count != need || !d->spectral_tables || uint64_t(n.table_offset) + need > d->n_spectral_table_values)
+		return msg.extent;
+	if (!(n.p[0] == 0.0f || n.p[0] == 1.0f))
+		return msg.interpolation;
+	for (int k = 1; k <= 2; ++k)
+		if (!(n.p[k] == 0.0f || n.p[k] == 1.0f || n.p[k] == 2.0f || n.p[k] == 3.0f))
+			return msg.wrap;
+	for (uint64_t k = 0; k < need; ++k)
+		if (!std::isfinite(d->spectral_tables[n.table_offset + k]))
+			return msg.finite;
+	if (msg.black && d->spectral_tables[n.table_offset + need - 1] != 0.0f)
+		return msg.black;
+	return nullptr;
+}
+// validate_desc's pass over the node array: every record's own requirements, and per node what the later checks read (`expr_info`,
+// `scalar_info`: filled in step, a node's from its operands', which precede it)
+int validate_nodes(const prgpu_scene_desc* d, std::vector<ExprInfo>& expr_info, std::vector<ScalarInfo>& scalar_info, std::string& err)
+{
+	auto bad = [&](const std::string& m, int code = PRGPU_EINVAL) {
+		err = m;
+		return code;
+	};
+	expr_info.reserve(d->n_spectra);
+	scalar_info.reserve(d->n_spectra);
+	for (uint32_t i = 0; i < d->n_spectra; ++i) {
+		const prgpu_spectrum& n = d->spectra[i];
+		if (n.kind > PRGPU_SPEC_SCALAR_COS || (n.kind > PRGPU_SPEC_PEAK && n.kind < PRGPU_SPEC_SCALAR_IMAGE))
+			return bad("unknown spectrum kind");
+		scalar_info.push_back(scalar_info_of(n, scalar_info));
+		if (scalar_is_kind(n.kind)) { // the scalar nodes: a family of their own (include/prgpu.h; DESIGN.md section 2.9)
+			const std::string what = "scalar node " + std::to_string(i);
+			if (d->n_spectra > 0x00FFFFFFu)
+				return bad("a scene with scalar nodes holds at most 2^24 - 1 nodes", PRGPU_EUNSUPPORTED);
+			if (n.kind == PRGPU_SPEC_SCALAR_IMAGE) {
+				if (const char* m = image_record_refusal(d, n, 1, SCALAR_IMAGE_REFUSALS))
+					return bad(m);
+			} else {
+				if (!program_operands_precede(SCALAR_FAMILY, n, i))
+					return bad(what + ": operands must precede the node");
+				for (uint32_t op : { n.lhs, scalar_is_unary(n.kind) ? n.lhs : n.rhs }) {
+					const prgpu_spectrum& o = d->spectra[op];
+					if (!scalar_is_kind(o.kind) && o.kind != PRGPU_SPEC_CONST)
+						return bad(what + ": a spectral node cannot stand where a scalar is expected (operands are scalar nodes or CONST)");
+					if (o.kind == PRGPU_SPEC_CONST && !std::isfinite(o.p[0]))
+						return bad(what + ": constant operands must be finite");
+				}
+				if (!(err = program_refusal(scalar_info[i], what)).empty())
+					return PRGPU_EUNSUPPORTED;
+			}
+			expr_info.push_back(ExprInfo());
+			continue;
+		}
+		if (spec_is_math(n.kind) || n.kind == PRGPU_SPEC_CHECKER) // (their own checks below refuse an operand that does not precede the node)
+			for (uint32_t op : { n.lhs, (n.kind != PRGPU_SPEC_MUL && n.kind != PRGPU_SPEC_CHECKER && spec_is_unary(n.kind)) ? n.lhs : n.rhs })
+				if (op < i && scalar_is_kind(d->spectra[op].kind))
+					return bad("spectral node " + std::to_string(i) + ": a scalar node cannot stand where a spectrum is expected", PRGPU_EUNSUPPORTED);
+		if (n.kind > PRGPU_SPEC_IMAGE) { // the expression nodes (MUL is checked below, as before)
+			const std::string what = "spectral expression node " + std::to_string(i);
+			if (d->n_spectra > 0x00FFFFFFu)
+				return bad("a scene with spectral expressions holds at most 2^24 - 1 spectral nodes", PRGPU_EUNSUPPORTED);
+			for (int k = 0; k < 4; ++k)
+				if (!std::isfinite(n.p[k]))
+					return bad(what + ": parameters must be finite");
+			if (n.kind == PRGPU_SPEC_BLACKBODY && !(n.p[0] > 0.0f))
+				return bad(what + ": blackbody temperature must be positive");
+			if (n.kind == PRGPU_SPEC_PEAK && !(n.p[1] > 0.0f))
+				return bad(what + ": peak radius must be positive");
+			if (spec_is_math(n.kind)) {
+				if (!program_operands_precede(SPEC_FAMILY, n, i))
+					return bad(what + ": operands must precede the node");
+				for (uint32_t op : { n.lhs, spec_is_unary(n.kind) ? n.lhs : n.rhs }) {
+					if (d->spectra[op].kind == PRGPU_SPEC_CHECKER)
+						return bad(what + ": a checkerboard inside a math node is not supported", PRGPU_EUNSUPPORTED);
+					if (d->spectra[op].kind == PRGPU_SPEC_IMAGE)
+						return bad(what + ": an image texture inside a math node is not supported", PRGPU_EUNSUPPORTED);
+				}
+			}
+		}
+		if (n.kind == PRGPU_SPEC_IMAGE)
+			if (const char* m = image_record_refusal(d, n, 4, SPECTRUM_IMAGE_REFUSALS))
+				return bad(m);
+		if (n.kind == PRGPU_SPEC_CHECKER && (n.lhs >= i || n.rhs >= i || !(n.p[2] == 0.0f || n.p[2] == 1.0f || n.p[2] == 2.0f)))
+			return bad("checkerboard operands must precede the node and its mode is 0, 1 or 2");
+		if (n.kind == PRGPU_SPEC_SELLMEIER && (n.table_count < 2 || n.table_count > 8 || (n.table_count & 1u) || uint64_t(n.table_offset) + n.table_count > d->n_spectral_table_values))
+			return bad("sellmeier coefficients out of range (1..4 B/C pairs in the table array)");
+		if (n.kind == PRGPU_SPEC_TABLE && (n.table_count < 2 || uint64_t(n.table_offset) + n.table_count > d->n_spectral_table_values || !(n.wl_end > n.wl_start)))
+			return bad("spectrum table out of range");
+		if (n.kind == PRGPU_SPEC_MUL) {
+			if (n.lhs >= i || n.rhs >= i)
+				return bad("MUL operands must precede the node");
+			if (d->n_spectra > 0x00FFFFFFu && (spec_is_math(d->spectra[n.lhs].kind) || spec_is_math(d->spectra[n.rhs].kind) || d->spectra[n.lhs].kind == PRGPU_SPEC_SELLMEIER || d->spectra[n.rhs].kind == PRGPU_SPEC_SELLMEIER))
+				return bad("a scene with spectral expressions holds at most 2^24 - 1 spectral nodes", PRGPU_EUNSUPPORTED);
+			if (d->spectra[n.lhs].kind == PRGPU_SPEC_CHECKER || d->spectra[n.rhs].kind == PRGPU_SPEC_CHECKER)
+				return bad("a checkerboard inside a MUL node is not supported", PRGPU_EUNSUPPORTED);
+			if (d->spectra[n.lhs].kind == PRGPU_SPEC_IMAGE || d->spectra[n.rhs].kind == PRGPU_SPEC_IMAGE)
+				return bad("an image texture inside a MUL node is not supported", PRGPU_EUNSUPPORTED);
+		}
+		expr_info.push_back(expr_info_of(n, expr_info, d->spectra));
+		if (expr_info[i].expression && !(err = program_refusal(expr_info[i], "spectral expression node " + std::to_string(i))).empty())
+			return PRGPU_EUNSUPPORTED;
+	}
+	return PRGPU_OK;
+}
+// The two steps compile_expressions and compile_scalar_nodes share.  A root's program (`emit`: the family's expr_emit / scalar_emit) is
+// appended to `programs`, which the device holds behind the scene's n_spectral_table_values floats, and named in the record's copy ...
+template <class Info, class Emit>
+void name_program(Emit emit, const prgpu_scene_desc* d, const std::vector<Info>& info, uint32_t root, prgpu_spectrum& copy, std::vector<uint32_t>& programs)
+{
+	const size_t first = programs.size();
+	emit(d->spectra, info, root, programs);
+	copy.table_offset = uint32_t(d->n_spectral_table_values + first);
+	copy.table_count  = uint32_t(programs.size() - first);
+}
+// ... and the copy of an operator's record that runs no program has the fields its kind does not use zeroed (table_count != 0 is a program)
+void name_no_program(prgpu_spectrum& copy)
+{
+	copy.table_offset = copy.table_count = 0;
+	copy.wl_start = copy.wl_end = 0.0f;
+}
 } // namespace
 
 int validate_desc(const prgpu_scene_desc* d, std::string& err)
@@ -1116,122 +1253,10 @@ int validate_desc(const prgpu_scene_desc* d, std::string& err)
 		if (E.kind == PRGPU_ENTITY_PLANE && E.n_tris != 2)
 			return bad("a plane entity is exactly two triangles (v0,v1,v3), (v2,v3,v1)");
 	}
-	std::vector<ExprInfo> expr_info; // per node, from its operands' (spectral_expr.h)
-	expr_info.reserve(d->n_spectra);
+	std::vector<ExprInfo> expr_info;	 // per node, from its operands' (spectral_expr.h)
 	std::vector<ScalarInfo> scalar_info; // the same for the scalar nodes (scalar_node.h)
-	scalar_info.reserve(d->n_spectra);
-	for (uint32_t i = 0; i < d->n_spectra; ++i) {
-		const prgpu_spectrum& n = d->spectra[i];
-		if (n.kind > PRGPU_SPEC_SCALAR_COS || (n.kind > PRGPU_SPEC_PEAK && n.kind < PRGPU_SPEC_SCALAR_IMAGE))
-			return bad("unknown spectrum kind");
-		scalar_info.push_back(scalar_info_of(n, scalar_info));
-		if (scalar_is_kind(n.kind)) { // the scalar nodes: a family of their own (include/prgpu.h; DESIGN.md section 2.9)
-			const std::string what = "scalar node " + std::to_string(i);
-			if (d->n_spectra > 0x00FFFFFFu)
-				return bad("a scene with scalar nodes holds at most 2^24 - 1 nodes", PRGPU_EUNSUPPORTED);
-			if (n.kind == PRGPU_SPEC_SCALAR_IMAGE) {
-				if (n.lhs == 0 || n.rhs == 0 || n.lhs > 4096 || n.rhs > 4096)
-					return bad("scalar image texture: width and height must be 1..4096");
-				const uint64_t need = uint64_t(n.lhs) * n.rhs + 1;
-				if (n.table_count != need || !d->spectral_tables || uint64_t(n.table_offset) + need > d->n_spectral_table_values)
-					return bad("scalar image texture: W H + 1 floats inside spectral_tables");
-				if (!(n.p[0] == 0.0f || n.p[0] == 1.0f))
-					return bad("scalar image texture: interpolation is 0 (closest) or 1 (bilinear)");
-				for (int k = 1; k <= 2; ++k)
-					if (!(n.p[k] == 0.0f || n.p[k] == 1.0f || n.p[k] == 2.0f || n.p[k] == 3.0f))
-						return bad("scalar image texture: wrap is 0 (black), 1 (clamp), 2 (periodic) or 3 (mirror)");
-				for (uint64_t k = 0; k < need; ++k)
-					if (!std::isfinite(d->spectral_tables[n.table_offset + k]))
-						return bad("scalar image texture: values must be finite");
-				if (d->spectral_tables[n.table_offset + need - 1] != 0.0f)
-					return bad("scalar image texture: the last value (the black texel) must be 0");
-			} else {
-				const bool unary = scalar_is_unary(n.kind);
-				if (n.lhs >= i || (!unary && n.rhs >= i))
-					return bad((what + ": operands must precede the node").c_str());
-				for (uint32_t op : { n.lhs, unary ? n.lhs : n.rhs }) {
-					const prgpu_spectrum& o = d->spectra[op];
-					if (!scalar_is_kind(o.kind) && o.kind != PRGPU_SPEC_CONST)
-						return bad((what + ": a spectral node cannot stand where a scalar is expected (operands are scalar nodes or CONST)").c_str());
-					if (o.kind == PRGPU_SPEC_CONST && !std::isfinite(o.p[0]))
-						return bad((what + ": constant operands must be finite").c_str());
-				}
-				if (scalar_info[i].need > PRGPU_EXPR_MAX_STACK)
-					return bad((what + ": needs an operand stack of " + std::to_string(scalar_info[i].need) + " entries, more than PRGPU_EXPR_MAX_STACK (" + std::to_string(PRGPU_EXPR_MAX_STACK) + ")").c_str(),
-							   PRGPU_EUNSUPPORTED);
-				if (scalar_info[i].length > PRGPU_EXPR_MAX_PROGRAM)
-					return bad((what + ": its program is longer than PRGPU_EXPR_MAX_PROGRAM (" + std::to_string(PRGPU_EXPR_MAX_PROGRAM) + " words)").c_str(), PRGPU_EUNSUPPORTED);
-			}
-			expr_info.push_back(ExprInfo());
-			continue;
-		}
-		if (spec_is_math(n.kind) || n.kind == PRGPU_SPEC_CHECKER) // (their own checks below refuse an operand that does not precede the node)
-			for (uint32_t op : { n.lhs, (n.kind != PRGPU_SPEC_MUL && n.kind != PRGPU_SPEC_CHECKER && spec_is_unary(n.kind)) ? n.lhs : n.rhs })
-				if (op < i && scalar_is_kind(d->spectra[op].kind))
-					return bad(("spectral node " + std::to_string(i) + ": a scalar node cannot stand where a spectrum is expected").c_str(), PRGPU_EUNSUPPORTED);
-		if (n.kind > PRGPU_SPEC_IMAGE) { // the expression nodes (MUL is checked below, as before)
-			const std::string what = "spectral expression node " + std::to_string(i);
-			if (d->n_spectra > 0x00FFFFFFu)
-				return bad("a scene with spectral expressions holds at most 2^24 - 1 spectral nodes", PRGPU_EUNSUPPORTED);
-			for (int k = 0; k < 4; ++k)
-				if (!std::isfinite(n.p[k]))
-					return bad((what + ": parameters must be finite").c_str());
-			if (n.kind == PRGPU_SPEC_BLACKBODY && !(n.p[0] > 0.0f))
-				return bad((what + ": blackbody temperature must be positive").c_str());
-			if (n.kind == PRGPU_SPEC_PEAK && !(n.p[1] > 0.0f))
-				return bad((what + ": peak radius must be positive").c_str());
-			if (spec_is_math(n.kind)) {
-				const bool unary = spec_is_unary(n.kind);
-				if (n.lhs >= i || (!unary && n.rhs >= i))
-					return bad((what + ": operands must precede the node").c_str());
-				for (uint32_t op : { n.lhs, unary ? n.lhs : n.rhs }) {
-					if (d->spectra[op].kind == PRGPU_SPEC_CHECKER)
-						return bad((what + ": a checkerboard inside a math node is not supported").c_str(), PRGPU_EUNSUPPORTED);
-					if (d->spectra[op].kind == PRGPU_SPEC_IMAGE)
-						return bad((what + ": an image texture inside a math node is not supported").c_str(), PRGPU_EUNSUPPORTED);
-				}
-			}
-		}
-		if (n.kind == PRGPU_SPEC_IMAGE) {
-			if (n.lhs == 0 || n.rhs == 0 || n.lhs > 4096 || n.rhs > 4096)
-				return bad("image texture: width and height must be 1..4096");
-			const uint64_t need = 4 * (uint64_t(n.lhs) * n.rhs + 1);
-			if (n.table_offset % 4 != 0 || n.table_count != need || !d->spectral_tables || uint64_t(n.table_offset) + need > d->n_spectral_table_values)
-				return bad("image texture: 4 (W H + 1) floats at a table_offset that is a multiple of 4, inside spectral_tables");
-			if (!(n.p[0] == 0.0f || n.p[0] == 1.0f))
-				return bad("image texture: interpolation is 0 (closest) or 1 (bilinear)");
-			for (int k = 1; k <= 2; ++k)
-				if (!(n.p[k] == 0.0f || n.p[k] == 1.0f || n.p[k] == 2.0f || n.p[k] == 3.0f))
-					return bad("image texture: wrap is 0 (black), 1 (clamp), 2 (periodic) or 3 (mirror)");
-			for (uint64_t k = 0; k < need; ++k)
-				if (!std::isfinite(d->spectral_tables[n.table_offset + k]))
-					return bad("image texture: texel coefficients must be finite");
-		}
-		if (n.kind == PRGPU_SPEC_CHECKER && (n.lhs >= i || n.rhs >= i || !(n.p[2] == 0.0f || n.p[2] == 1.0f || n.p[2] == 2.0f)))
-			return bad("checkerboard operands must precede the node and its mode is 0, 1 or 2");
-		if (n.kind == PRGPU_SPEC_SELLMEIER && (n.table_count < 2 || n.table_count > 8 || (n.table_count & 1u) || uint64_t(n.table_offset) + n.table_count > d->n_spectral_table_values))
-			return bad("sellmeier coefficients out of range (1..4 B/C pairs in the table array)");
-		if (n.kind == PRGPU_SPEC_TABLE && (n.table_count < 2 || uint64_t(n.table_offset) + n.table_count > d->n_spectral_table_values || !(n.wl_end > n.wl_start)))
-			return bad("spectrum table out of range");
-		if (n.kind == PRGPU_SPEC_MUL) {
-			if (n.lhs >= i || n.rhs >= i)
-				return bad("MUL operands must precede the node");
-			if (d->n_spectra > 0x00FFFFFFu && (spec_is_math(d->spectra[n.lhs].kind) || spec_is_math(d->spectra[n.rhs].kind) || d->spectra[n.lhs].kind == PRGPU_SPEC_SELLMEIER || d->spectra[n.rhs].kind == PRGPU_SPEC_SELLMEIER))
-				return bad("a scene with spectral expressions holds at most 2^24 - 1 spectral nodes", PRGPU_EUNSUPPORTED);
-			if (d->spectra[n.lhs].kind == PRGPU_SPEC_CHECKER || d->spectra[n.rhs].kind == PRGPU_SPEC_CHECKER)
-				return bad("a checkerboard inside a MUL node is not supported", PRGPU_EUNSUPPORTED);
-			if (d->spectra[n.lhs].kind == PRGPU_SPEC_IMAGE || d->spectra[n.rhs].kind == PRGPU_SPEC_IMAGE)
-				return bad("an image texture inside a MUL node is not supported", PRGPU_EUNSUPPORTED);
-		}
-		expr_info.push_back(expr_info_of(n, expr_info, d->spectra));
-		if (expr_info[i].expression && expr_info[i].need > PRGPU_EXPR_MAX_STACK)
-			return bad(("spectral expression node " + std::to_string(i) + ": needs an operand stack of " + std::to_string(expr_info[i].need) + " entries, more than PRGPU_EXPR_MAX_STACK ("
-						+ std::to_string(PRGPU_EXPR_MAX_STACK) + ")")
-						   .c_str(),
-					   PRGPU_EUNSUPPORTED);
-		if (expr_info[i].expression && expr_info[i].length > PRGPU_EXPR_MAX_PROGRAM)
-			return bad(("spectral expression node " + std::to_string(i) + ": its program is longer than PRGPU_EXPR_MAX_PROGRAM (" + std::to_string(PRGPU_EXPR_MAX_PROGRAM) + " words)").c_str(), PRGPU_EUNSUPPORTED);
-	}
+	if (const int rc = validate_nodes(d, expr_info, scalar_info, err))
+		return rc;
 	std::vector<MixExtent> mix_extent(d->n_materials);
 	for (uint32_t i = 0; i < d->n_materials; ++i) {
 		const prgpu_material& m = d->materials[i];
@@ -1436,20 +1461,15 @@ bool compile_expressions(const prgpu_scene_desc* d, std::vector<prgpu_spectrum>&
 		if (!root[i])
 			continue;
 		any = true;
-		const size_t first = programs.size();
-		expr_emit(d->spectra, info, i, programs);
-		spectra[i].table_offset = uint32_t(d->n_spectral_table_values + first);
-		spectra[i].table_count	= uint32_t(programs.size() - first);
+		name_program(expr_emit, d, info, i, spectra[i], programs);
 		spectra[i].wl_start		= info[i].varying ? 1.0f : 0.0f;
 		spectra[i].wl_end		= 0.0f;
 	}
 	// A node that is no root runs no program, whatever the caller left in fields its kind does not use -- in EVERY scene: the top row's
 	// kernels look at table_count of a MUL whether or not the scene has a root (a scene gets there for a disk or a light path expression too).
 	for (uint32_t i = 0; i < d->n_spectra; ++i)
-		if (!root[i] && (spectra[i].kind == PRGPU_SPEC_MUL || (spectra[i].kind > PRGPU_SPEC_IMAGE && spectra[i].kind <= PRGPU_SPEC_PEAK))) { // (a scalar node is compile_scalar_nodes')
-			spectra[i].table_offset = spectra[i].table_count = 0;
-			spectra[i].wl_start = spectra[i].wl_end = 0.0f;
-		}
+		if (!root[i] && (spectra[i].kind == PRGPU_SPEC_MUL || (spectra[i].kind > PRGPU_SPEC_IMAGE && spectra[i].kind <= PRGPU_SPEC_PEAK))) // (a scalar node is compile_scalar_nodes')
+			name_no_program(spectra[i]);
 	return any;
 }
 
@@ -1473,14 +1493,9 @@ bool compile_scalar_nodes(const prgpu_scene_desc* d, std::vector<prgpu_spectrum>
 	for (uint32_t i = 0; i < d->n_spectra; ++i) {
 		if (!scalar_is_op(spectra[i].kind))
 			continue;
-		spectra[i].table_offset = spectra[i].table_count = 0;
-		spectra[i].wl_start = spectra[i].wl_end = 0.0f;
-		if (!root[i])
-			continue;
-		const size_t first = programs.size();
-		scalar_emit(d->spectra, info, i, programs);
-		spectra[i].table_offset = uint32_t(d->n_spectral_table_values + first);
-		spectra[i].table_count	= uint32_t(programs.size() - first);
+		name_no_program(spectra[i]);
+		if (root[i])
+			name_program(scalar_emit, d, info, i, spectra[i], programs);
 	}
 	return any;
 }

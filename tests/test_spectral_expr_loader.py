@@ -4,10 +4,11 @@ prgpu_scene_create's validation refuse -- the validation runs before any device 
 
 The host evaluator is reached through the one place the library exposes it: a `sky` light's ground `:albedo` is evaluated by the loader at the eleven
 band wavelengths of the sky model, 320 + 40 k nm (prgpu_prc_sky_info).  400 nm is one of them; 550 and 700 nm are not, 560 and 680 / 720 nm stand in
-for them.  The other copy (host/setup.cpp: light power, the spd histogram) is not reachable without a device; it calls the same expr_eval_at of
-host/spectral_expr.h, operators and leaves, that this test holds to float64.  tests/test_gpu_spectral_expr.py renders under the `spd` mapper, whose
-histogram that copy fills, against the `random` one: that shows a usable density, not its values (importance sampling is unbiased under any positive
-pdf).  spectral_range() of the new kinds (union / pass-through / unbounded) has no observable on either side and is covered by reading only."""
+for them.  The host has ONE evaluator: expr_eval_at and spectrum_leaf_at of host/spectral_expr.h, over the arithmetic the kernels compile too
+(device/node_math.h), which this test holds to float64.  Its other caller (host/setup.cpp: light power, the spd histogram) is not reachable without
+a device; tests/test_gpu_spectral_expr.py renders under the `spd` mapper, whose histogram that caller fills, against the `random` one: that shows a
+usable density, not its values (importance sampling is unbiased under any positive pdf).  spectral_range() of the new kinds (union / pass-through /
+unbounded) has no observable on either side and is covered by reading only."""
 import ctypes as C
 import math
 
