@@ -546,6 +546,47 @@ int  prgpu_trace_closest(prgpu_scene* s, uint32_t n, const float* org, const flo
 int  prgpu_trace_any(prgpu_scene* s, uint32_t n, const float* org, const float* dir,
                      const float* tmin, const float* distance, uint8_t* occluded);
 
+/* The same service on memory the caller already holds on the scene's device (a PyTorch tensor's data_ptr(), the output of a kernel of the
+ * caller's), with the hit's shading geometry.  Both calls ENQUEUE on the scene's stream (prgpu_set_stream) and return: no host
+ * synchronisation, no copy, and no allocation while n is at most what an earlier call or prgpu_ray_service_reserve sized the scene's
+ * scratch for (16 bytes per ray: the winning triangle's scene-wide index, and room for u, v, t where the caller passes NULL for them but
+ * asks for geometry; a call with a larger n grows it once, which waits for the device).  n == 0 is PRGPU_OK and launches nothing.
+ *
+ * Answers are those of the host entry points for the same rays, bit for bit: the same kernels run.  The geometry is the pipelines'
+ * GeometryPoint of the hit (IEntity::provideGeometryPoint) evaluated at position = org + dir * t -- bit for bit what a pipeline adds to its
+ * shading-point planes (prgpu_enable_aovs) for the same ray, with what that implies: uv of a sphere, a disk and a quadric is 0, a quadric's
+ * normal is not normalised again, a mesh without normals gets the frame of its edge vectors, a plane's uv is the quad's (u, v) on its first
+ * triangle and (1-u, 1-v) on its second (both report prim 0).  On a miss the geometry floats are 0 and the ids PRGPU_INVALID_ID.
+ *
+ * Refused rays: the host entry points refuse a batch with a negative or NaN tmin before any launch; these cannot read the array, so a
+ * ray with !(tmin >= 0) is answered as a miss (occluded = 0) and counted in *invalid -- ONE counter per call site, incremented once per
+ * refused ray, which the caller zeroes; NULL: not counted, the ray is a miss all the same.  A ray whose origin is not finite is a miss
+ * as in every other entry point, and is not counted.
+ *
+ * Before anything is enqueued every non-NULL pointer is checked (hipPointerGetAttributes): one that is not device memory of the scene's
+ * device gives PRGPU_EINVAL, and prgpu_last_error() names the field.  The size of the allocation behind a pointer is the caller's business.
+ *
+ * The traversal workspace and the scratch belong to the scene object: calls on one scene -- these, prgpu_trace_closest / _any and
+ * prgpu_render alike -- must be ordered on its stream, or separated by prgpu_sync; never issue them from two threads or two streams at once.
+ * With prgpu_set_timing on, the traversal launches count in "trace_closest" / "trace_any" and the geometry pass in "geometry". */
+typedef struct prgpu_rays {        /* DEVICE pointers on the scene's device */
+	uint32_t n;
+	const float *org, *dir;        /* 3*n, xyz per ray, as prgpu_trace_closest takes them */
+	const float *tmin, *tmax;      /* n each; for prgpu_trace_any_device tmax is the distance */
+} prgpu_rays;
+typedef struct prgpu_hits {        /* DEVICE pointers, every one may be NULL */
+	uint32_t *entity, *prim;       /* PRGPU_INVALID_ID on a miss */
+	float *u, *v, *t;              /* as prgpu_trace_closest: 0, 0, tmax[i] on a miss */
+	float *position;               /* 3*n: org + dir * t */
+	float *normal, *tangent, *bitangent; /* 3*n each: GeometryPoint N, Nx, Ny */
+	float *uv;                     /* 2*n: GeometryPoint UV */
+	uint32_t *material, *emission; /* n each; emission PRGPU_INVALID_ID when the entity has none */
+	uint32_t *invalid;             /* ONE counter, incremented per refused ray; the caller zeroes it */
+} prgpu_hits;
+int  prgpu_trace_closest_device(prgpu_scene* s, const prgpu_rays* rays, const prgpu_hits* hits);
+int  prgpu_trace_any_device(prgpu_scene* s, const prgpu_rays* rays, uint8_t* occluded, uint32_t* invalid);
+int  prgpu_ray_service_reserve(prgpu_scene* s, uint32_t n); /* size the scratch for batches of up to n rays (never shrinks) */
+
 /* Primary-visibility debug plane of the LAST rendered iteration (entity, prim per pixel; host arrays
  * of W*H u32).  Used by the hit-id parity tests. */
 int  prgpu_download_primary_hits(prgpu_scene* s, uint32_t* entity, uint32_t* prim);
@@ -553,7 +594,7 @@ int  prgpu_download_primary_hits(prgpu_scene* s, uint32_t* entity, uint32_t* pri
 /* Time the traversal kernels alone on the rays recorded during the last iteration is not part of the
  * ABI; bench.py measures kernels with HIP events through prgpu_kernel_time_ms(). */
 /* Accumulated HIP-event time [ms] and launch count of a named kernel family since scene creation
- * ("trace_closest", "trace_any", "shade", "raygen", "resolve", "sort", "path", "reduce", "ao", "vf"). Requires prgpu_set_timing(s,1). */
+ * ("trace_closest", "trace_any", "shade", "raygen", "resolve", "sort", "path", "reduce", "ao", "vf", "geometry"). Requires prgpu_set_timing(s,1). */
 int  prgpu_set_timing(prgpu_scene* s, int enabled);
 int  prgpu_kernel_time_ms(prgpu_scene* s, const char* family, double* total_ms, uint64_t* launches);
 

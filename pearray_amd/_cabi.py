@@ -143,6 +143,16 @@ class TraceCounters(C.Structure):
                 ("shade_ticks", C.c_uint64), ("idle_ticks", C.c_uint64), ("total_ticks", C.c_uint64)]
 
 
+class Rays(C.Structure):  # prgpu_rays: DEVICE pointers
+    _fields_ = [("n", C.c_uint32), ("org", C.c_void_p), ("dir", C.c_void_p), ("tmin", C.c_void_p), ("tmax", C.c_void_p)]
+
+
+class Hits(C.Structure):  # prgpu_hits: DEVICE pointers, every one may be NULL
+    _fields_ = [("entity", C.c_void_p), ("prim", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("t", C.c_void_p),
+                ("position", C.c_void_p), ("normal", C.c_void_p), ("tangent", C.c_void_p), ("bitangent", C.c_void_p), ("uv", C.c_void_p),
+                ("material", C.c_void_p), ("emission", C.c_void_p), ("invalid", C.c_void_p)]
+
+
 class ImageStats(C.Structure):
     _fields_ = [("n", C.c_uint64), ("min", C.c_float), ("min_ref", C.c_float), ("min_diff", C.c_float), ("max", C.c_float),
                 ("max_ref", C.c_float), ("max_diff", C.c_float), ("mean", C.c_float), ("mean_ref", C.c_float), ("mean_diff", C.c_float),
@@ -216,6 +226,9 @@ SYMBOLS = {
     "prgpu_set_instrumentation": (C.c_int, [_VP, C.c_int]),
     "prgpu_trace_closest": (C.c_int, [_VP, C.c_uint32, _F32P, _F32P, _F32P, _F32P, _U32P, _U32P, _F32P, _F32P, _F32P]),
     "prgpu_trace_any": (C.c_int, [_VP, C.c_uint32, _F32P, _F32P, _F32P, _F32P, _U8P]),
+    "prgpu_trace_closest_device": (C.c_int, [_VP, C.POINTER(Rays), C.POINTER(Hits)]),
+    "prgpu_trace_any_device": (C.c_int, [_VP, C.POINTER(Rays), _VP, _VP]),
+    "prgpu_ray_service_reserve": (C.c_int, [_VP, C.c_uint32]),
     "prgpu_download_primary_hits": (C.c_int, [_VP, _U32P, _U32P]),
     "prgpu_set_timing": (C.c_int, [_VP, C.c_int]),
     "prgpu_kernel_time_ms": (C.c_int, [_VP, C.c_char_p, C.POINTER(C.c_double), _U64P]),

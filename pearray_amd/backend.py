@@ -6,6 +6,7 @@ create -> start -> wait -> save) and the `direct` integrator contract (IIntegrat
 ``statistics()`` returns the RenderStatistics counters and ``output()`` the XYZ / sample-count planes.
 All compute goes through ``libprgpu.so``; there is no CPU path here.
 """
+import collections
 import ctypes as C
 import os
 
@@ -22,6 +23,54 @@ def _u32p(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint32))
 
 
+def check_ray_tensors(org, direction, tmin, tmax, device, last="tmax"):
+    """The argument checks of RenderContext.traceRaysDevice / traceShadowRaysDevice (last="distance"); needs no device.  `org` and
+    `direction`: float32 CUDA tensors of shape (n, 3); `tmin` and the last argument: float32 CUDA tensors of shape (n,), or Python
+    floats (the wrapper expands those on the device).  Every tensor contiguous and on device index `device`.  Returns n; anything
+    else raises ValueError naming the argument."""
+    import torch
+
+    def tensor(name, a, n, tail):
+        """float32, shape (n,) + tail (n None: any length), contiguous"""
+        want = "(n%s)" % "".join(", %d" % k for k in tail) if tail else "(n,)"
+        if not isinstance(a, torch.Tensor):
+            raise ValueError("%s: a torch tensor is expected, not %s" % (name, type(a).__name__))
+        if a.dtype != torch.float32:
+            raise ValueError("%s: float32 is expected, not %s" % (name, a.dtype))
+        if a.dim() != 1 + len(tail) or tuple(a.shape[1:]) != tail:
+            raise ValueError("%s: shape %s is expected, not %s" % (name, want, tuple(a.shape)))
+        if n is not None and a.shape[0] != n:
+            raise ValueError("%s: %d rays are expected as in org, not %d" % (name, n, a.shape[0]))
+        if not a.is_contiguous():
+            raise ValueError("%s: the tensor is not contiguous" % name)
+
+    tensor("org", org, None, (3,))
+    n = int(org.shape[0])
+    if n >= 1 << 32:
+        raise ValueError("org: more than 2^32 - 1 rays")
+    tensor("direction", direction, n, (3,))
+    given = [("org", org), ("direction", direction)]
+    for name, a in (("tmin", tmin), (last, tmax)):
+        if isinstance(a, (int, float)) and not isinstance(a, bool):
+            continue
+        tensor(name, a, n, ())
+        given.append((name, a))
+    for name, a in given:   # where the tensors live comes last, so that a test without a device reaches every check above
+        if not a.is_cuda:
+            raise ValueError("%s: the tensor is on %s, not on the GPU (traceRays / traceShadowRays take host arrays)" % (name, a.device))
+        if a.device.index != int(device):
+            raise ValueError("%s: the tensor is on %s, the scene on device %d" % (name, a.device, int(device)))
+    return n
+
+
+RayHits = collections.namedtuple("RayHits", "entity prim u v t")
+RayHitsCounted = collections.namedtuple("RayHitsCounted", RayHits._fields + ("invalid",))
+_GEOMETRY = ("position", "normal", "tangent", "bitangent", "uv", "material", "emission")
+RayGeometry = collections.namedtuple("RayGeometry", RayHits._fields + _GEOMETRY)
+RayGeometryCounted = collections.namedtuple("RayGeometryCounted", RayGeometry._fields + ("invalid",))
+ShadowRaysCounted = collections.namedtuple("ShadowRaysCounted", "occluded invalid")
+
+
 class RenderContext:
     """One scene resident on one GPU (mirrors renderer/RenderContext.h + Scene + `direct` integrator)."""
 
@@ -31,6 +80,9 @@ class RenderContext:
         self._h = C.c_void_p()
         abi.check(self.lib.prgpu_scene_create(C.byref(scene.desc), int(device), C.byref(self._h)))
         self.width, self.height = scene.width, scene.height
+        self.device = int(device)
+        self._stream = None      # the stream handle setStream was given last (None: the scene's own)
+        self._lent_to = None     # the torch stream the scene runs on since a device ray batch (None: it is on its own)
         self.iterations_done = 0
         self.ao_sample_count = 0
         if getattr(scene, "integrator", abi.INTEGRATOR_DIRECT) == abi.INTEGRATOR_AO:   # (integrator :type 'ao') / SceneBuilder.ambient_occlusion
@@ -59,6 +111,13 @@ class RenderContext:
 
     def setStream(self, stream_handle):
         abi.check(self.lib.prgpu_set_stream(self._h, C.c_void_p(stream_handle)))
+        self._stream, self._lent_to = stream_handle, None
+
+    def _stream_home(self):
+        """After traceRaysDevice / traceShadowRaysDevice the scene is still on torch's stream: put it back on the one it had."""
+        if self._lent_to is not None:
+            abi.check(self.lib.prgpu_set_stream(self._h, C.c_void_p(self._stream)))
+            self._lent_to = None
 
     def bindFramebuffer(self, xyz_ptr, samples_ptr, feedback_ptr=None):
         abi.check(self.lib.prgpu_bind_framebuffer(self._h, C.c_void_p(xyz_ptr), C.c_void_p(samples_ptr),
@@ -68,6 +127,7 @@ class RenderContext:
         """Sum every rank's frame into planes the library keeps on `root` (RCCL over xGMI); asynchronous on the scene's stream.  The
         rank's own planes -- and a framebuffer bound with bindFramebuffer -- keep the rank's OWN pixels: on the root output() /
         outputAOV() / ... read the sums until the next render call, and reducedPlanes() hands out their device pointers."""
+        self._stream_home()
         abi.check(self.lib.prgpu_reduce(self._h, comm._h, int(root)))
 
     def reducedPlanes(self):
@@ -95,6 +155,7 @@ class RenderContext:
     # -- rendering ----------------------------------------------------------------------------------------
     def render(self, iterations):
         """Render the next `iterations` iterations (one camera sample per owned pixel each)."""
+        self._stream_home()
         b = self.iterations_done
         abi.check(self.lib.prgpu_render(self._h, b, b + int(iterations)))
         self.iterations_done = b + int(iterations)
@@ -104,6 +165,7 @@ class RenderContext:
         self.render(self.scene.spp - self.iterations_done)
 
     def waitForFinish(self):
+        self._stream_home()
         abi.check(self.lib.prgpu_sync(self._h))
 
     def statistics(self):
@@ -240,6 +302,7 @@ class RenderContext:
         tmax = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,)))
         ent, prim = np.empty(n, np.uint32), np.empty(n, np.uint32)
         u, v, t = np.empty(n, np.float32), np.empty(n, np.float32), np.empty(n, np.float32)
+        self._stream_home()
         abi.check(self.lib.prgpu_trace_closest(self._h, n, _f32p(org), _f32p(direction), _f32p(tmin), _f32p(tmax),
                                                _u32p(ent), _u32p(prim), _f32p(u), _f32p(v), _f32p(t)))
         return ent, prim, u, v, t
@@ -251,9 +314,76 @@ class RenderContext:
         tmin = np.ascontiguousarray(np.broadcast_to(np.asarray(tmin, dtype=np.float32), (n,)))
         distance = np.ascontiguousarray(np.broadcast_to(np.asarray(distance, dtype=np.float32), (n,)))
         occ = np.empty(n, np.uint8)
+        self._stream_home()
         abi.check(self.lib.prgpu_trace_any(self._h, n, _f32p(org), _f32p(direction), _f32p(tmin), _f32p(distance),
                                            occ.ctypes.data_as(C.POINTER(C.c_uint8))))
         return occ.astype(bool)
+
+    # -- the same service on tensors that live on the GPU --------------------------------------------------------
+    def reserveRays(self, n):
+        """Size the ray service's scratch for device batches of up to `n` rays, so that none of them allocates."""
+        abi.check(self.lib.prgpu_ray_service_reserve(self._h, int(n)))
+
+    def _on_torch_stream(self):
+        """Order the scene with torch: it runs on torch's current stream from here on, behind the work that made the rays and ahead of
+        the work that reads the answers.  prgpu_sync first: a render in flight on the scene's stream has finished (and a device-side
+        error of it is reported here).  The scene STAYS on that stream until the next call that is not a device ray batch puts it back
+        (_stream_home): prgpu_set_stream waits for the stream it leaves, so putting it back at once would wait for the launch.  Batch
+        after batch on one torch stream neither waits nor switches."""
+        import torch
+        handle = torch.cuda.current_stream(self.device).cuda_stream or 1   # 1: hipStreamLegacy, the null stream's own handle (0 would mean "the scene's own stream")
+        if self._lent_to != handle:
+            abi.check(self.lib.prgpu_sync(self._h))
+            abi.check(self.lib.prgpu_set_stream(self._h, C.c_void_p(handle)))
+            self._lent_to = handle
+
+    @staticmethod
+    def _per_ray(a, n, like):
+        import torch
+        return a if isinstance(a, torch.Tensor) else torch.full((n,), float(a), dtype=torch.float32, device=like.device)
+
+    def traceRaysDevice(self, org, direction, tmin, tmax, geometry=False, count_invalid=False):
+        """traceRays on CUDA tensors, where they are (check_ray_tensors states what is accepted): enqueued on torch's current stream, no
+        copy and no synchronisation -- the answers are tensors this call allocates, to be read by later work on that stream.
+        Returns a named tuple (entity, prim, u, v, t), with geometry=True followed by (position [n, 3], normal, tangent, bitangent,
+        uv [n, 2], material, emission) -- the hit's GeometryPoint, bit for bit what a render adds to its AOV planes for the same ray --
+        and with count_invalid=True by `invalid`, a one-element int32 tensor: the rays with a negative or NaN tmin, which are answered
+        as misses (traceRays refuses such a batch).  Ids are int32 tensors that hold the uint32 bits: a miss (PRGPU_INVALID_ID) reads -1.
+        On a miss u = v = 0, t = tmax, the geometry is 0 and its ids are -1."""
+        import torch
+        n = check_ray_tensors(org, direction, tmin, tmax, self.device)
+        with torch.cuda.device(self.device):
+            tmin, tmax = self._per_ray(tmin, n, org), self._per_ray(tmax, n, org)
+            f32, i32 = dict(dtype=torch.float32, device=org.device), dict(dtype=torch.int32, device=org.device)
+            out = [torch.empty(n, **i32), torch.empty(n, **i32), torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, **f32)]
+            if geometry:
+                out += [torch.empty((n, 3), **f32) for _ in range(4)] + [torch.empty((n, 2), **f32), torch.empty(n, **i32), torch.empty(n, **i32)]
+            invalid = torch.zeros(1, **i32) if count_invalid else None
+            rays = abi.Rays(n, org.data_ptr(), direction.data_ptr(), tmin.data_ptr(), tmax.data_ptr())
+            hits = abi.Hits(*[a.data_ptr() for a in out])   # (the fields of prgpu_hits in order; without geometry the rest stay NULL)
+            hits.invalid = invalid.data_ptr() if count_invalid else None
+            if n:
+                self._on_torch_stream()
+                abi.check(self.lib.prgpu_trace_closest_device(self._h, C.byref(rays), C.byref(hits)))
+        kind = (RayGeometryCounted if count_invalid else RayGeometry) if geometry else (RayHitsCounted if count_invalid else RayHits)
+        return kind(*(out + ([invalid] if count_invalid else [])))
+
+    def traceShadowRaysDevice(self, org, direction, tmin, distance, count_invalid=False):
+        """traceShadowRays on CUDA tensors, enqueued on torch's current stream as traceRaysDevice is: a bool tensor `occluded` -- anything
+        in [tmin, distance - 0.001] --, or with count_invalid=True the named tuple (occluded, invalid): rays with a negative or NaN tmin
+        are not occluded and counted."""
+        import torch
+        n = check_ray_tensors(org, direction, tmin, distance, self.device, last="distance")
+        with torch.cuda.device(self.device):
+            tmin, distance = self._per_ray(tmin, n, org), self._per_ray(distance, n, org)
+            occluded = torch.empty(n, dtype=torch.bool, device=org.device)   # one byte each: the kernel writes 0 or 1
+            invalid = torch.zeros(1, dtype=torch.int32, device=org.device) if count_invalid else None
+            rays = abi.Rays(n, org.data_ptr(), direction.data_ptr(), tmin.data_ptr(), distance.data_ptr())
+            if n:
+                self._on_torch_stream()
+                abi.check(self.lib.prgpu_trace_any_device(self._h, C.byref(rays), C.c_void_p(occluded.data_ptr()),
+                                                          C.c_void_p(invalid.data_ptr()) if count_invalid else None))
+        return ShadowRaysCounted(occluded, invalid) if count_invalid else occluded
 
 
 class Communicator:

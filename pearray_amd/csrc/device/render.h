@@ -172,6 +172,24 @@ void launch_service_closest_split(const DevScene& sc, uint32_t n, const float* o
 								  unsigned long long* gstats, bool leaf_single /* the tree's leaves are single leaves */, hipStream_t st); // prototype, see render.hip
 void launch_service_any(const DevScene& sc, uint32_t n, const float* org, const float* dir, const float* tmin, const float* distance,
 						uint8_t* occluded, const TraceWorkspace& ws, unsigned long long* gstats, hipStream_t st);
+// The ray service on caller-owned DEVICE memory (prgpu_trace_closest_device / prgpu_trace_any_device): the same traversal kernels, compiled with
+// the refused-ray rule (a ray with !(tmin >= 0) is a miss and counts in *invalid) and a NULL test per output, and the geometry pass behind them.
+struct ServiceRays {
+	uint32_t n;
+	const float *org, *dir, *tmin, *tmax; // tmax: the distance of an occlusion ray
+};
+struct ServiceHits { // every pointer may be null, except -- for launch_service_geometry -- tri, u, v, t, which it reads
+	uint32_t *entity, *prim;
+	float *u, *v, *t;
+	uint32_t* tri; // the winning triangle's scene-wide index (INVALID on a miss)
+	float *position, *normal, *tangent, *bitangent, *uv;
+	uint32_t *material, *emission, *invalid;
+};
+void launch_service_closest_device(const DevScene& sc, const ServiceRays& r, const ServiceHits& h, bool split, const TraceWorkspace& ws, uint32_t* tri_slot,
+								   unsigned long long* gstats, bool leaf_single, hipStream_t st);
+void launch_service_any_device(const DevScene& sc, const ServiceRays& r, uint8_t* occluded, uint32_t* invalid, const TraceWorkspace& ws, unsigned long long* gstats,
+							   hipStream_t st);
+void launch_service_geometry(const DevScene& sc, const ServiceRays& r, const ServiceHits& h, hipStream_t st); // GeomPoint of every ray that hit, zeros / INVALID for the others
 // What prgpu_enable_ambient_occlusion allocates; passed by value.
 struct AoState {
 	float4* rec;			// 4 per hit: (P, slot bits), (N, state low), (Nx, state high), (Ny, 0)

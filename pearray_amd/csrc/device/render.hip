@@ -3360,27 +3360,68 @@ __device__ __forceinline__ PathCie slot_cie(const PathState& ps, uint32_t slot)
 #include "vf.inl"
 
 // ---- ray service kernels (IArchive surface) ------------------------------------------------------------
-__global__ void __launch_bounds__(TRAV_BLOCK) k_service_closest(DevScene sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,
-															   const float* __restrict__ tmin_a, const float* __restrict__ tmax_a, uint32_t* entity,
-															   uint32_t* prim, float* u, float* v, float* t, uint32_t* queue_head, uint2* spill,
-															   int refill_below, unsigned long long* gstats)
+// Every service kernel exists twice: for the host entry points (prgpu_trace_closest / prgpu_trace_any: the batch was checked on the host, every
+// output is written) and, DEVICE, for the entry points on caller-owned device memory (prgpu_trace_closest_device / prgpu_trace_any_device):
+//   * a ray with !(tmin >= 0) -- the host entry points refuse such a batch before any launch -- is ended where it is born, the way sane_ray ends
+//     a ray without a finite origin (extent -inf: no child of the root passes), answered as a miss whatever the walk found, and counted in
+//     *invalid (one atomic per refused ray; NULL: not counted);
+//   * every output may be NULL (a uniform branch per output), and tri_out takes the winning triangle's scene-wide index for k_service_geometry.
+// One body per kernel, compiled for either; the host kernels keep their names, their parameters and their code.
+template <bool DEVICE>
+__device__ __forceinline__ bool service_refused(float& tmin, float& tmax, uint32_t* invalid)
+{
+	if (!DEVICE || tmin >= 0.0f)
+		return false;
+	tmin = 0.0f;
+	tmax = -INFINITY;
+	if (invalid)
+		atomicAdd(invalid, 1u);
+	return true;
+}
+template <bool DEVICE>
+__device__ __forceinline__ void service_closest(const DevScene& sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,
+												const float* __restrict__ tmin_a, const float* __restrict__ tmax_a, uint32_t* entity, uint32_t* prim, float* u,
+												float* v, float* t, uint32_t* tri_out, uint32_t* invalid, uint32_t* queue_head, uint2* spill, int refill_below,
+												unsigned long long* gstats)
 {
 	auto load = [&](uint32_t i, V3& o, V3& d, float& tmin, float& tmax) {
 		o	 = v3(org[3 * i], org[3 * i + 1], org[3 * i + 2]);
 		d	 = v3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
 		tmin = tmin_a[i];
 		tmax = tmax_a[i];
+		(void)service_refused<DEVICE>(tmin, tmax, invalid);
 	};
 	auto store = [&](uint32_t i, const Hit& h) {
-		const bool ok	 = h.tri != INVALID;
+		const bool ok	 = h.tri != INVALID && (!DEVICE || tmin_a[i] >= 0.0f);
 		const uint32_t e = ok ? sc.tri_entity[h.tri] : INVALID;
-		entity[i]		 = e;
-		prim[i]			 = ok ? prim_id(sc, h.tri) : INVALID;
-		u[i]			 = ok ? h.u : 0.0f;
-		v[i]			 = ok ? h.v : 0.0f;
-		t[i]			 = ok ? h.t : tmax_a[i];
+		if (!DEVICE || entity)
+			entity[i] = e;
+		if (!DEVICE || prim)
+			prim[i] = ok ? prim_id(sc, h.tri) : INVALID;
+		if (!DEVICE || u)
+			u[i] = ok ? h.u : 0.0f;
+		if (!DEVICE || v)
+			v[i] = ok ? h.v : 0.0f;
+		if (!DEVICE || t)
+			t[i] = ok ? h.t : tmax_a[i];
+		if (DEVICE && tri_out)
+			tri_out[i] = ok ? h.tri : INVALID;
 	};
 	trace_persistent<false, true>(sc, n, queue_head, spill, refill_below, load, store, gstats);
+}
+__global__ void __launch_bounds__(TRAV_BLOCK) k_service_closest(DevScene sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,
+															   const float* __restrict__ tmin_a, const float* __restrict__ tmax_a, uint32_t* entity,
+															   uint32_t* prim, float* u, float* v, float* t, uint32_t* queue_head, uint2* spill,
+															   int refill_below, unsigned long long* gstats)
+{
+	service_closest<false>(sc, n, org, dir, tmin_a, tmax_a, entity, prim, u, v, t, nullptr, nullptr, queue_head, spill, refill_below, gstats);
+}
+__global__ void __launch_bounds__(TRAV_BLOCK) k_service_closest_device(DevScene sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,
+																	  const float* __restrict__ tmin_a, const float* __restrict__ tmax_a, uint32_t* entity,
+																	  uint32_t* prim, float* u, float* v, float* t, uint32_t* tri_out, uint32_t* invalid,
+																	  uint32_t* queue_head, uint2* spill, int refill_below, unsigned long long* gstats)
+{
+	service_closest<true>(sc, n, org, dir, tmin_a, tmax_a, entity, prim, u, v, t, tri_out, invalid, queue_head, spill, refill_below, gstats);
 }
 // ---- ray service, closest hit (default; PRGPU_TRACE_SPLIT=0 selects k_service_closest): leaf tests handed to whole waves through an LDS task queue ----
 // A wave step of the production traversal serves ONE kind of record, so 42 % of the lanes idle (lane utilisation 0.58).  Here a lane
@@ -3466,11 +3507,11 @@ __global__ void k_tri_slot(DevScene sc, const uint32_t* __restrict__ leaf_units,
 	for (uint32_t k = 0; k < cnt && k < 3u; ++k)
 		tri_slot[__float_as_uint(f[10 * k + 9]) & PRIM_INDEX_MASK] = (unit << 2) | k;
 }
-template <bool WIDE>
-__global__ void __launch_bounds__(TRAV_BLOCK) k_service_closest_split(DevScene sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,
-																	 const float* __restrict__ tmin_a, const float* __restrict__ tmax_a, uint32_t* entity,
-																	 uint32_t* prim, float* u, float* v, float* t, uint32_t* queue_head, uint2* spill,
-																	 const uint32_t* __restrict__ tri_slot, int refill_below, unsigned long long* gstats, bool leaf_single)
+template <bool WIDE, bool DEVICE>
+__device__ __forceinline__ void service_closest_split(const DevScene& sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,
+													  const float* __restrict__ tmin_a, const float* __restrict__ tmax_a, uint32_t* entity, uint32_t* prim,
+													  float* u, float* v, float* t, uint32_t* tri_out, uint32_t* invalid, uint32_t* queue_head, uint2* spill,
+													  const uint32_t* __restrict__ tri_slot, int refill_below, unsigned long long* gstats, bool leaf_single)
 {
 	constexpr uint32_t SQ = SplitRing<WIDE>::N;
 	__shared__ SplitShared<WIDE> sh;
@@ -3552,18 +3593,25 @@ __global__ void __launch_bounds__(TRAV_BLOCK) k_service_closest_split(DevScene s
 		// rays that are done: one more test of the winning triangle for u, v (batched here, outside the stepping loop)
 		if (drained) {
 			const unsigned long long key = __hip_atomic_load(&sh.best[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-			const uint32_t tri			 = (uint32_t)key;
+			const uint32_t tri			 = DEVICE && !(tmin_a[my_ray] >= 0.0f) ? INVALID : (uint32_t)key; // (a refused ray is a miss whatever the walk found)
 			float tt = tmax_a[my_ray], uu = 0.0f, vv = 0.0f;
 			if (tri != INVALID) {
 				const uint32_t slot = tri_slot[tri];
 				const float* f		= reinterpret_cast<const float*>(sc.recs + (slot >> 2)) + 10u * (slot & 3u);
 				(void)woop(s.r, v3(f[0], f[1], f[2]), v3(f[3], f[4], f[5]), v3(f[6], f[7], f[8]), tt, uu, vv);
 			}
-			entity[my_ray] = tri != INVALID ? sc.tri_entity[tri] : INVALID;
-			prim[my_ray]   = tri != INVALID ? prim_id(sc, tri) : INVALID;
-			u[my_ray]	   = uu;
-			v[my_ray]	   = vv;
-			t[my_ray]	   = tt;
+			if (!DEVICE || entity)
+				entity[my_ray] = tri != INVALID ? sc.tri_entity[tri] : INVALID;
+			if (!DEVICE || prim)
+				prim[my_ray] = tri != INVALID ? prim_id(sc, tri) : INVALID;
+			if (!DEVICE || u)
+				u[my_ray] = uu;
+			if (!DEVICE || v)
+				v[my_ray] = vv;
+			if (!DEVICE || t)
+				t[my_ray] = tt;
+			if (DEVICE && tri_out)
+				tri_out[my_ray] = tri;
 			has_ray		   = false;
 			drained		   = false;
 		}
@@ -3579,9 +3627,10 @@ __global__ void __launch_bounds__(TRAV_BLOCK) k_service_closest_split(DevScene s
 					const uint32_t i = base + __popcll(idle & ((1ull << lane) - 1ull));
 					if (i < n) {
 						const V3 o = v3(org[3 * i], org[3 * i + 1], org[3 * i + 2]), d = v3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
-						float tmax_i = tmax_a[i];
+						float tmin_i = tmin_a[i], tmax_i = tmax_a[i];
+						(void)service_refused<DEVICE>(tmin_i, tmax_i, invalid);
 						const V3 so = sane_ray(o, tmax_i);
-						trav_begin(s, st, so, d, tmin_a[i], tmax_i, sc.eps_t);
+						trav_begin(s, st, so, d, tmin_i, tmax_i, sc.eps_t);
 						sh.rc[0][tid] = make_float4(so.x, so.y, so.z, __uint_as_float((uint32_t)s.r.kx | ((uint32_t)s.r.ky << 2) | ((uint32_t)s.r.kz << 4)));
 						sh.rc[1][tid] = make_float4(s.r.Sx, s.r.Sy, s.r.Sz, s.tmin);
 						__hip_atomic_store(&sh.best[tid], ((unsigned long long)__float_as_uint(tmax_i) << 32) | 0xFFFFFFFFull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -3647,18 +3696,97 @@ __global__ void __launch_bounds__(TRAV_BLOCK) k_service_closest_split(DevScene s
 	if (witers)
 		atomicAdd(&gstats[CNT_WAVE_ITERS_CLOSEST], (unsigned long long)witers);
 }
-__global__ void __launch_bounds__(TRAV_BLOCK) k_service_any(DevScene sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,
-														   const float* __restrict__ tmin_a, const float* __restrict__ distance, uint8_t* occluded,
-														   uint32_t* queue_head, uint2* spill, int refill_below, unsigned long long* gstats)
+template <bool WIDE>
+__global__ void __launch_bounds__(TRAV_BLOCK) k_service_closest_split(DevScene sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,
+																	 const float* __restrict__ tmin_a, const float* __restrict__ tmax_a, uint32_t* entity,
+																	 uint32_t* prim, float* u, float* v, float* t, uint32_t* queue_head, uint2* spill,
+																	 const uint32_t* __restrict__ tri_slot, int refill_below, unsigned long long* gstats, bool leaf_single)
+{
+	service_closest_split<WIDE, false>(sc, n, org, dir, tmin_a, tmax_a, entity, prim, u, v, t, nullptr, nullptr, queue_head, spill, tri_slot, refill_below, gstats, leaf_single);
+}
+template <bool WIDE>
+__global__ void __launch_bounds__(TRAV_BLOCK) k_service_closest_split_device(DevScene sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,
+																			const float* __restrict__ tmin_a, const float* __restrict__ tmax_a, uint32_t* entity,
+																			uint32_t* prim, float* u, float* v, float* t, uint32_t* tri_out, uint32_t* invalid,
+																			uint32_t* queue_head, uint2* spill, const uint32_t* __restrict__ tri_slot, int refill_below,
+																			unsigned long long* gstats, bool leaf_single)
+{
+	service_closest_split<WIDE, true>(sc, n, org, dir, tmin_a, tmax_a, entity, prim, u, v, t, tri_out, invalid, queue_head, spill, tri_slot, refill_below, gstats, leaf_single);
+}
+template <bool DEVICE>
+__device__ __forceinline__ void service_any(const DevScene& sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,
+											const float* __restrict__ tmin_a, const float* __restrict__ distance, uint8_t* occluded, uint32_t* invalid,
+											uint32_t* queue_head, uint2* spill, int refill_below, unsigned long long* gstats)
 {
 	auto load = [&](uint32_t i, V3& o, V3& d, float& tmin, float& tmax) {
 		o	 = v3(org[3 * i], org[3 * i + 1], org[3 * i + 2]);
 		d	 = v3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
 		tmin = tmin_a[i];
 		tmax = distance[i] - 0.001f;
+		(void)service_refused<DEVICE>(tmin, tmax, invalid);
 	};
-	auto store = [&](uint32_t i, const Hit& h) { occluded[i] = h.tri != INVALID ? 1 : 0; };
+	auto store = [&](uint32_t i, const Hit& h) { occluded[i] = h.tri != INVALID && (!DEVICE || tmin_a[i] >= 0.0f) ? 1 : 0; };
 	trace_persistent<true, true>(sc, n, queue_head, spill, refill_below, load, store, gstats);
+}
+__global__ void __launch_bounds__(TRAV_BLOCK) k_service_any(DevScene sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,
+														   const float* __restrict__ tmin_a, const float* __restrict__ distance, uint8_t* occluded,
+														   uint32_t* queue_head, uint2* spill, int refill_below, unsigned long long* gstats)
+{
+	service_any<false>(sc, n, org, dir, tmin_a, distance, occluded, nullptr, queue_head, spill, refill_below, gstats);
+}
+__global__ void __launch_bounds__(TRAV_BLOCK) k_service_any_device(DevScene sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,
+																  const float* __restrict__ tmin_a, const float* __restrict__ distance, uint8_t* occluded,
+																  uint32_t* invalid, uint32_t* queue_head, uint2* spill, int refill_below, unsigned long long* gstats)
+{
+	service_any<true>(sc, n, org, dir, tmin_a, distance, occluded, invalid, queue_head, spill, refill_below, gstats);
+}
+// ---- ray service, geometry pass (prgpu_trace_closest_device with any of position .. emission) ----------------------------------------------
+// One lane per ray, after the traversal kernel of the same call: (tri, u, v, t) are that kernel's answers, the geometry is
+// geometry_point<FEAT_ALL & ~FEAT_LPE> at P = org + dir * t -- the statement and the instantiation of camera_vertex above, so the values are the
+// bits a pipeline commits to its shading-point planes for the same ray.  A ray that missed gets zeros and PRGPU_INVALID_ID.  Every output may
+// be NULL (a uniform branch each).  A lane reads its triangle's 128-byte shading record and writes 12- and 8-byte records at lane stride.
+// Not part of the traversal kernels' store: geometry_point with every branch compiled in would sit in the register budget of their loop.
+struct ServiceGeometry {
+	float *position, *normal, *tangent, *bitangent, *uv;
+	uint32_t *material, *emission;
+};
+__global__ void __launch_bounds__(256) k_service_geometry(DevScene sc, uint32_t n, const float* __restrict__ org, const float* __restrict__ dir,
+														  const uint32_t* __restrict__ tri_a, const float* __restrict__ u_a, const float* __restrict__ v_a,
+														  const float* __restrict__ t_a, ServiceGeometry out)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n)
+		return;
+	const uint32_t tri = tri_a[i];
+	V3 P = v3(0.0f, 0.0f, 0.0f);
+	GeomPoint gp;
+	gp.N = gp.Nx = gp.Ny = P;
+	gp.uv[0] = gp.uv[1] = 0.0f;
+	gp.entity = gp.prim = gp.material = gp.emission = INVALID;
+	if (tri != INVALID) {
+		const V3 ray_o = v3(org[3 * i], org[3 * i + 1], org[3 * i + 2]), ray_d = v3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
+		P = ray_o + ray_d * t_a[i];
+		geometry_point<(FEAT_ALL & ~FEAT_LPE)>(sc, tri, u_a[i], v_a[i], P, gp);
+	}
+	auto put3 = [&](float* a, V3 w) {
+		if (a) {
+			a[3 * i]	 = w.x;
+			a[3 * i + 1] = w.y;
+			a[3 * i + 2] = w.z;
+		}
+	};
+	put3(out.position, P);
+	put3(out.normal, gp.N);
+	put3(out.tangent, gp.Nx);
+	put3(out.bitangent, gp.Ny);
+	if (out.uv) {
+		out.uv[2 * i]	  = gp.uv[0];
+		out.uv[2 * i + 1] = gp.uv[1];
+	}
+	if (out.material)
+		out.material[i] = gp.material;
+	if (out.emission)
+		out.emission[i] = gp.emission;
 }
 
 // ---- launchers ----------------------------------------------------------------------------------------------
@@ -3779,6 +3907,33 @@ void launch_service_any(const DevScene& sc, uint32_t n, const float* org, const 
 	(void)hipMemsetAsync(ws.queue_head, 0, sizeof(uint32_t), st);
 	hipLaunchKernelGGL(k_service_any, trav_grid(ws, n), dim3(TRAV_BLOCK), 0, st, sc, n, org, dir, tmin, distance, occluded, ws.queue_head, ws.spill,
 					   ws.refill_below, gstats);
+}
+void launch_service_closest_device(const DevScene& sc, const ServiceRays& r, const ServiceHits& h, bool split, const TraceWorkspace& ws, uint32_t* tri_slot,
+								   unsigned long long* gstats, bool leaf_single, hipStream_t st)
+{
+	(void)hipMemsetAsync(ws.queue_head, 0, sizeof(uint32_t), st);
+	const dim3 g = trav_grid(ws, r.n);
+	if (!split)
+		hipLaunchKernelGGL(k_service_closest_device, g, dim3(TRAV_BLOCK), 0, st, sc, r.n, r.org, r.dir, r.tmin, r.tmax, h.entity, h.prim, h.u, h.v, h.t, h.tri, h.invalid,
+						   ws.queue_head, ws.spill, ws.refill_below, gstats);
+	else if (sc.bvh_wide)
+		hipLaunchKernelGGL(k_service_closest_split_device<true>, g, dim3(TRAV_BLOCK), 0, st, sc, r.n, r.org, r.dir, r.tmin, r.tmax, h.entity, h.prim, h.u, h.v, h.t, h.tri,
+						   h.invalid, ws.queue_head, ws.spill, tri_slot, ws.refill_below, gstats, leaf_single);
+	else
+		hipLaunchKernelGGL(k_service_closest_split_device<false>, g, dim3(TRAV_BLOCK), 0, st, sc, r.n, r.org, r.dir, r.tmin, r.tmax, h.entity, h.prim, h.u, h.v, h.t, h.tri,
+						   h.invalid, ws.queue_head, ws.spill, tri_slot, ws.refill_below, gstats, leaf_single);
+}
+void launch_service_any_device(const DevScene& sc, const ServiceRays& r, uint8_t* occluded, uint32_t* invalid, const TraceWorkspace& ws, unsigned long long* gstats,
+							   hipStream_t st)
+{
+	(void)hipMemsetAsync(ws.queue_head, 0, sizeof(uint32_t), st);
+	hipLaunchKernelGGL(k_service_any_device, trav_grid(ws, r.n), dim3(TRAV_BLOCK), 0, st, sc, r.n, r.org, r.dir, r.tmin, r.tmax, occluded, invalid, ws.queue_head, ws.spill,
+					   ws.refill_below, gstats);
+}
+void launch_service_geometry(const DevScene& sc, const ServiceRays& r, const ServiceHits& h, hipStream_t st)
+{
+	const ServiceGeometry out = { h.position, h.normal, h.tangent, h.bitangent, h.uv, h.material, h.emission };
+	hipLaunchKernelGGL(k_service_geometry, grid_for(r.n), dim3(256), 0, st, sc, r.n, r.org, r.dir, h.tri, h.u, h.v, h.t, out);
 }
 void launch_ao_hits(const DevScene& sc, const PathState& ps, const AoState& ao, uint32_t n_slots, bool instrumented, uint32_t* n_hits, uint32_t* queue_head_closest,
 					uint32_t* queue_head_ao, unsigned long long* gstats, hipStream_t st)

@@ -173,8 +173,8 @@ struct TimedLaunch {
 	hipEvent_t start, stop;
 	int family;
 };
-enum Family { FAM_RAYGEN, FAM_TRACE_CLOSEST, FAM_SHADE, FAM_TRACE_ANY, FAM_RESOLVE, FAM_SORT, FAM_PATH, FAM_REDUCE, FAM_AO, FAM_VF, N_FAMILIES };
-const char* const FAMILY_NAMES[] = { "raygen", "trace_closest", "shade", "trace_any", "resolve", "sort", "path", "reduce", "ao", "vf" }; // in the order of Family
+enum Family { FAM_RAYGEN, FAM_TRACE_CLOSEST, FAM_SHADE, FAM_TRACE_ANY, FAM_RESOLVE, FAM_SORT, FAM_PATH, FAM_REDUCE, FAM_AO, FAM_VF, FAM_GEOMETRY, N_FAMILIES };
+const char* const FAMILY_NAMES[] = { "raygen", "trace_closest", "shade", "trace_any", "resolve", "sort", "path", "reduce", "ao", "vf", "geometry" }; // in the order of Family
 static_assert(sizeof(FAMILY_NAMES) / sizeof(FAMILY_NAMES[0]) == N_FAMILIES, "one name per timing family");
 
 } // namespace
@@ -212,6 +212,8 @@ struct prgpu_scene {
 	unsigned long long* gstats = nullptr;
 	prd::TraceWorkspace ws;	   // workspace of the ray-service launches
 	prd::TraceWorkspace ws_pp; // grid geometry and stack spill slab of the persistent path kernel
+	uint32_t* svc_scratch = nullptr; // ray service on device memory: 4 * svc_rays words -- per ray the winning triangle, then room for u, v, t the caller left out
+	uint32_t svc_rays = 0;			 // rays the scratch holds (prgpu_ray_service_reserve; grown by a larger batch)
 	// Pixel groups: contiguous ranges of the Morton-ordered slot list, each running its own wavefront pipeline on
 	// its own pair of HIP streams so that the latency tails of one group's kernels overlap the other groups' work.
 	struct Group {
@@ -1440,6 +1442,7 @@ void prgpu_scene_destroy(prgpu_scene* s)
 	s->collect_timing();
 	for (void* p : s->allocations)
 		(void)hipFree(p);
+	(void)hipFree(s->svc_scratch);
 	for (auto& g : s->groups) {
 		if (g.h_counters)
 			(void)hipHostFree(g.h_counters);
@@ -1785,6 +1788,154 @@ int prgpu_trace_any(prgpu_scene* s, uint32_t n, const float* org, const float* d
 	TRY_OR_CLEAN(hipStreamSynchronize(s->stream));
 	TRY_OR_CLEAN(hipMemcpy(occluded, d_occ, size_t(n), hipMemcpyDeviceToHost));
 	cleanup();
+	return PRGPU_OK;
+}
+
+// ---- ray service on caller-owned device memory ------------------------------------------------------------------------------------------
+} // extern "C" (helpers)
+namespace {
+// The check that stands between a caller's mistake and a memory fault: `p` must be device memory of the scene's device.  A pageable host
+// pointer answers with an error or as unregistered memory, depending on the runtime: both are refused (and the runtime's error is cleared).
+int service_pointer(const prgpu_scene* s, const void* p, const char* call, const char* field)
+{
+	if (!p)
+		return PRGPU_OK;
+	hipPointerAttribute_t a{};
+	const hipError_t e = hipPointerGetAttributes(&a, p);
+	if (e != hipSuccess)
+		(void)hipGetLastError();
+	if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != s->device)
+		return fail(PRGPU_EINVAL, std::string(call) + ": " + field + " is not device memory of the scene's device");
+	return PRGPU_OK;
+}
+int service_reserve(prgpu_scene* s, uint32_t n)
+{
+	if (n <= s->svc_rays)
+		return PRGPU_OK;
+	HIP_TRY(hipStreamSynchronize(s->stream)); // a launch in flight may still read the old block
+	(void)hipFree(s->svc_scratch);
+	s->svc_scratch = nullptr;
+	s->svc_rays	   = 0;
+	void* p		   = nullptr;
+	HIP_TRY(hipMalloc(&p, size_t(n) * 16));
+	s->svc_scratch = static_cast<uint32_t*>(p);
+	s->svc_rays	   = n;
+	return PRGPU_OK;
+}
+#define SERVICE_POINTER(call, obj, field)                                                \
+	do {                                                                                 \
+		const int _rc = service_pointer(s, (obj)->field, call, #field);                  \
+		if (_rc != PRGPU_OK)                                                             \
+			return _rc;                                                                  \
+	} while (0)
+} // namespace
+extern "C" {
+
+int prgpu_ray_service_reserve(prgpu_scene* s, uint32_t n)
+{
+	if (!s)
+		return fail(PRGPU_EINVAL, "prgpu_ray_service_reserve: null scene");
+	HIP_TRY(hipSetDevice(s->device));
+	return service_reserve(s, n);
+}
+
+int prgpu_trace_closest_device(prgpu_scene* s, const prgpu_rays* rays, const prgpu_hits* hits)
+{
+	static const char* const CALL = "prgpu_trace_closest_device";
+	if (!rays)
+		return fail(PRGPU_EINVAL, std::string(CALL) + ": rays is NULL");
+	if (!hits)
+		return fail(PRGPU_EINVAL, std::string(CALL) + ": hits is NULL");
+	if (!s)
+		return fail(PRGPU_EINVAL, std::string(CALL) + ": null scene");
+	const uint32_t n = rays->n;
+	if (n && (!rays->org || !rays->dir || !rays->tmin || !rays->tmax))
+		return fail(PRGPU_EINVAL, std::string(CALL) + ": " + (!rays->org ? "org" : !rays->dir ? "dir" : !rays->tmin ? "tmin" : "tmax") + " is NULL");
+	HIP_TRY(hipSetDevice(s->device));
+	SERVICE_POINTER(CALL, rays, org);
+	SERVICE_POINTER(CALL, rays, dir);
+	SERVICE_POINTER(CALL, rays, tmin);
+	SERVICE_POINTER(CALL, rays, tmax);
+	SERVICE_POINTER(CALL, hits, entity);
+	SERVICE_POINTER(CALL, hits, prim);
+	SERVICE_POINTER(CALL, hits, u);
+	SERVICE_POINTER(CALL, hits, v);
+	SERVICE_POINTER(CALL, hits, t);
+	SERVICE_POINTER(CALL, hits, position);
+	SERVICE_POINTER(CALL, hits, normal);
+	SERVICE_POINTER(CALL, hits, tangent);
+	SERVICE_POINTER(CALL, hits, bitangent);
+	SERVICE_POINTER(CALL, hits, uv);
+	SERVICE_POINTER(CALL, hits, material);
+	SERVICE_POINTER(CALL, hits, emission);
+	SERVICE_POINTER(CALL, hits, invalid);
+	if (n == 0)
+		return PRGPU_OK;
+	const bool geometry = hits->position || hits->normal || hits->tangent || hits->bitangent || hits->uv || hits->material || hits->emission;
+	const prd::ServiceRays r = { n, rays->org, rays->dir, rays->tmin, rays->tmax };
+	prd::ServiceHits h = { hits->entity, hits->prim, hits->u, hits->v, hits->t, nullptr, hits->position, hits->normal, hits->tangent, hits->bitangent,
+						   hits->uv, hits->material, hits->emission, hits->invalid };
+	if (geometry) { // the geometry pass reads (tri, u, v, t): the scratch holds what the caller did not ask for
+		const int rc = service_reserve(s, n);
+		if (rc != PRGPU_OK)
+			return rc;
+		const size_t cap = s->svc_rays;
+		h.tri = s->svc_scratch;
+		if (!h.u)
+			h.u = reinterpret_cast<float*>(s->svc_scratch + cap);
+		if (!h.v)
+			h.v = reinterpret_cast<float*>(s->svc_scratch + 2 * cap);
+		if (!h.t)
+			h.t = reinterpret_cast<float*>(s->svc_scratch + 3 * cap);
+	}
+	s->time_begin(FAM_TRACE_CLOSEST, s->stream);
+	const bool split = read_knobs().trace_split && s->sc.n_leaf > 0 && s->bvh_units < (1u << 24)
+					   && !(s->sc.features & (prd::FEAT_SPHERES | prd::FEAT_QUADRICS | prd::FEAT_DISKS)); // as prgpu_trace_closest chooses
+	prd::launch_service_closest_device(s->sc, r, h, split, s->ws, const_cast<uint32_t*>(s->sc.tri_slot), s->gstats, s->bvh_leaf == 1, s->stream);
+	s->time_end(s->stream);
+	s->rays_closest += n;
+	HIP_TRY(hipGetLastError());
+	if (geometry) {
+		s->time_begin(FAM_GEOMETRY, s->stream);
+		prd::launch_service_geometry(s->sc, r, h, s->stream);
+		s->time_end(s->stream);
+		HIP_TRY(hipGetLastError());
+	}
+	return PRGPU_OK;
+}
+
+int prgpu_trace_any_device(prgpu_scene* s, const prgpu_rays* rays, uint8_t* occluded, uint32_t* invalid)
+{
+	static const char* const CALL = "prgpu_trace_any_device";
+	if (!rays)
+		return fail(PRGPU_EINVAL, std::string(CALL) + ": rays is NULL");
+	if (!occluded)
+		return fail(PRGPU_EINVAL, std::string(CALL) + ": occluded is NULL");
+	if (!s)
+		return fail(PRGPU_EINVAL, std::string(CALL) + ": null scene");
+	const uint32_t n = rays->n;
+	if (n && (!rays->org || !rays->dir || !rays->tmin || !rays->tmax))
+		return fail(PRGPU_EINVAL, std::string(CALL) + ": " + (!rays->org ? "org" : !rays->dir ? "dir" : !rays->tmin ? "tmin" : "tmax") + " is NULL");
+	HIP_TRY(hipSetDevice(s->device));
+	SERVICE_POINTER(CALL, rays, org);
+	SERVICE_POINTER(CALL, rays, dir);
+	SERVICE_POINTER(CALL, rays, tmin);
+	SERVICE_POINTER(CALL, rays, tmax);
+	{
+		int rc = service_pointer(s, occluded, CALL, "occluded");
+		if (rc == PRGPU_OK)
+			rc = service_pointer(s, invalid, CALL, "invalid");
+		if (rc != PRGPU_OK)
+			return rc;
+	}
+	if (n == 0)
+		return PRGPU_OK;
+	const prd::ServiceRays r = { n, rays->org, rays->dir, rays->tmin, rays->tmax };
+	s->time_begin(FAM_TRACE_ANY, s->stream);
+	prd::launch_service_any_device(s->sc, r, occluded, invalid, s->ws, s->gstats, s->stream);
+	s->time_end(s->stream);
+	s->rays_any += n;
+	HIP_TRY(hipGetLastError());
 	return PRGPU_OK;
 }
 
