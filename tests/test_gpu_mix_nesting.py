@@ -20,8 +20,8 @@ flattened coefficients add at most four roundings of 6e-8, any error of rule is 
  9  A Cornell box with a depth-3 tree (principled and Sellmeier-glass leaves), a sub-tree with two parents and a depth-one blend renders to the same frame,
     sample counts and statistics, bit for bit, in every pipeline.  (pipelineInfo does not expose the shade class of a triangle.)
 
-Not pinned here: the pdf a sampled level contributes (observable only through multiple importance sampling at a later vertex) and the order of the
-draws across levels; both restate blend.cpp:104-122 / add.cpp:92-110."""
+Not pinned here: the pdf a sampled level contributes (observable only through multiple importance sampling at a later vertex: tests/test_gpu_mix_mis.py
+holds it) and the order of the draws across levels, which no statistic sees; both restate blend.cpp:104-122 / add.cpp:92-110."""
 import numpy as np
 import pytest
 
